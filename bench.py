@@ -5,7 +5,9 @@ Workload (N=1): BASELINE.json configs[2] — 1M partitions x 5 replicas,
 steady-state append + commit: every tick each leader appends one block and
 receives the 4 follower acks of the previous tick.  The
 synthetic AppendEntries-ack stream for all warm-up + timed ticks is generated
-on the device BEFORE the timed region, so inputs are resident in HBM.  For
+on the device BEFORE the timed region, so inputs are resident in HBM (when it
+does not fit, in buffer-sized runs of ticks, the clock stopped while the next
+run is generated).  For
 N>1 (one process per GPU: launched by torch.distributed.run, or - when plain
 `python bench.py --gpus N` is run without a launcher - by bench.py re-executing
 itself under torch.distributed.run; WORLD_SIZE must equal --gpus either way)
@@ -14,7 +16,7 @@ collective: Raft groups are independent — SURVEY.md §8(e)).
 
 A "step" = one tick = one launch of k_leader_tick_dense<5> over the rank's
 groups.  Timing: barrier + synchronize, then exactly K steps; a rank's clock stops
-when its own K steps are complete (HIP event + synchronize), the closing barrier
+when its own K steps are complete (HIP event + synchronize; --steps K is exactly the steps timed), the closing barrier
 follows, and the MAX over ranks is what is reported (the latency of the barrier
 collective itself is not part of anybody's K steps).  Prints ONE JSON line on rank 0.
 """
@@ -1151,6 +1153,37 @@ def self_launch(args):
     raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
+DUMP_MAX_GROUPS = 131072  # groups per column --dump-outputs writes: 1 MiB of float64 a column, 41 columns at R = 8 (under 64 MB)
+DUMP_SAMPLE_SEED = 0x64756D70
+
+
+def dump_outputs(out_dir, eng, extra=None):
+    """--dump-outputs: the engine's readable state columns, what a caller of the timed path reads back after its last step,
+    as DIR/<name>.npy in float64 - every group, or a fixed seeded sample of DUMP_MAX_GROUPS groups (their indices in
+    sample_groups.npy).  64-bit columns are written as their low and high 32-bit halves (<name>_lo32, <name>_hi32) so
+    that float64 holds them exactly; match is one file per replica (match<r>_...).  `extra`: more arrays, as given."""
+    import numpy as np
+    from josefine_amd import capi
+
+    os.makedirs(out_dir, exist_ok=True)
+    G = eng.G
+    idx = np.arange(G) if G <= DUMP_MAX_GROUPS else \
+        np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(G, DUMP_MAX_GROUPS, replace=False))
+    cols = {"sample_groups": idx.astype(np.float64)}
+    for name in capi.FIELD_NAMES:
+        for r in (range(eng.R) if name == "match" else [0]):
+            v = eng.read(name, r)[idx]
+            key = f"match{r}" if name == "match" else name
+            if v.dtype.itemsize == 8:
+                cols[key + "_lo32"] = (v & np.uint64(0xFFFFFFFF)).astype(np.float64)
+                cols[key + "_hi32"] = (v >> np.uint64(32)).astype(np.float64)
+            else:
+                cols[key] = v.astype(np.float64)
+    cols.update(extra or {})
+    for k, v in cols.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(v, dtype=np.float64))
+
+
 def devices_config(args, world):
     """config entries that say where the ranks ran"""
     devs = getattr(args, "devices_bound", [0])
@@ -1230,9 +1263,18 @@ def main():
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x6A6F736566696E65)
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed - the engine's state columns after the last step "
+                         "(rank 0's shard; a fixed sample of groups when it is large) and the timed steps' counters - as "
+                         "DIR/<name>.npy in float64; the headline path (with --mode / --failures / --ticks-per-launch) only")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs and (args.cluster or args.any_leader or args.single_process or args.event_loop or args.config == 4):
+        raise SystemExit("--dump-outputs is implemented for the headline path only (no --cluster / --any-leader / "
+                         "--single-process / --event-loop / --config 4)")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)  # (ranks and sub-runs may not share the working directory)
     if args.vote_words is None:
         args.vote_words = (1 if args.replicas >= 5 else 0) if args.any_leader else 1
     if args.config == 3:
@@ -1296,15 +1338,40 @@ def main():
     eng.drain_messages(), eng.drain_applies()
     api, h = eng.api, eng._h
 
-    # pre-generate the whole ack stream in HBM: (W+K) ticks x [R][G] u64
+    # The ack stream is generated in HBM before it is applied: a buffer of S ticks x [R][G] u64 that holds all W + K ticks
+    # when they fit in half of the device memory that is free (the ranks that share a device share it), else it is refilled
+    # with the next S ticks whenever the ticks reach its end - outside the clock.  The generator's state runs on across
+    # refills, so the stream is the same whatever S is (JG_BENCH_STREAM_TICKS caps S, to check exactly that).
     tick_bytes = R * G * 8
+    sharing = args.devices_bound.count(dev_index)
+    S = max(1, min(W + K, torch.cuda.mem_get_info(dev_index)[0] // (2 * sharing * tick_bytes)))
+    if os.environ.get("JG_BENCH_STREAM_TICKS"):
+        S = max(1, min(S, int(os.environ["JG_BENCH_STREAM_TICKS"])))
+    if world > 1:  # (every rank cuts its steps at the same ticks)
+        st = torch.tensor([S], dtype=torch.int64, device=red_dev)
+        dist.all_reduce(st, op=dist.ReduceOp.MIN)
+        S = int(st.item())
     sim = C.c_void_p()
     stream_buf = C.c_void_p()
     eng._check(api.device_alloc(h, tick_bytes, C.byref(sim)))
-    eng._check(api.device_alloc(h, tick_bytes * (W + K), C.byref(stream_buf)))
-    for t in range(W + K):
-        eng._check(api.synth_fill_acks_device(h, args.mode, t, sim, C.c_void_p(stream_buf.value + t * tick_bytes)))
-    eng._check(api.sync(h))
+    eng._check(api.device_alloc(h, tick_bytes * S, C.byref(stream_buf)))
+    stream = {"base": 0, "next": 0}  # the buffer holds ticks [base, base + S); the generator's next tick
+
+    def fill(t):
+        """ticks [t, t + S) of the stream into the buffer (the generator continues where it stopped)"""
+        assert t == stream["next"], (t, stream)
+        for i in range(S):
+            eng._check(api.synth_fill_acks_device(h, args.mode, t + i, sim, C.c_void_p(stream_buf.value + i * tick_bytes)))
+        eng._check(api.sync(h))
+        stream["base"], stream["next"] = t, t + S
+
+    def buffered_until(t):
+        """the end of the run of ticks from t that the buffer holds, refilling it from t when t is past its end"""
+        if t >= stream["base"] + S:
+            fill(t)
+        return stream["base"] + S
+
+    fill(0)
 
     def barrier():
         if world > 1:
@@ -1330,7 +1397,7 @@ def main():
         t = t0_
         while t < t1_:
             n = min(T, t1_ - t)
-            ptr = C.c_void_p(stream_buf.value + t * tick_bytes)
+            ptr = C.c_void_p(stream_buf.value + (t - stream["base"]) * tick_bytes)
             if n == 1:
                 eng._check(api.step_dense_acks_device(h, ptr))
             else:
@@ -1362,62 +1429,58 @@ def main():
         drained["applies"] += len(eng.drain_applies(copy=False))
         drained["faults"] += len(eng.drain_faults())
 
-    run_ticks(0, W)
+    t = 0
+    while t < W:  # the warm-up, through as many buffer fills as it takes
+        t1 = min(W, buffered_until(t))
+        run_ticks(t, t1)
+        t = t1
     if fail_rows is not None:  # one more full drain cycle outside the timed region (pinned queues at their working size)
         eng.drain_flush()
         consume()
         eng._check(api.kernel_timing(h, 4))  # (every 4th dense launch: the event pair is not free in a tick of three small kernels)
     barrier()
     c0 = eng.counters()
-    barrier()
-    t0 = time.perf_counter()
-    eng._check(api.timer_start(h))
-    n_launches = run_ticks(W, W + K)
-    ev_ms = C.c_float(0)
-    eng._check(api.timer_stop(h, C.byref(ev_ms)))  # HIP events on the engine's stream (synchronises it)
-    torch.cuda.synchronize()
-    wall = time.perf_counter() - t0  # this rank's K steps are done; MAX over ranks below
-    barrier()
-    c1 = eng.counters()
 
-    decisions = c1["decisions"] - c0["decisions"]
-    # A timed region of a few hundred microseconds is mostly the launch latency of its first kernel and the completion
-    # wake-up of its last (~45 us whatever K is): when K steps take less than 50 ms the region is REPEATED - the same K
-    # steps over the next K ticks of the stream, barrier and synchronisation on both sides each time - and the MEDIAN
-    # region is reported (`steps` stays K: one region; every region is listed in `timed_regions`).
-    ticks_done = W + K
-    regions = [(wall, ev_ms.value)]
-    if T == 1 and not args.failures and args.mode == 0:
-        all_short = torch.tensor([1.0 if wall < 0.05 else 0.0], dtype=torch.float64, device=red_dev)
-        if world > 1:
-            dist.all_reduce(all_short, op=dist.ReduceOp.MIN)  # (every rank takes the same number of regions)
-        n_more = 8 if all_short.item() > 0 else 0
-        for _ in range(n_more):
-            for t in range(K):  # the next K ticks of the stream into the slots of W .. W+K-1
-                eng._check(api.synth_fill_acks_device(h, 0, ticks_done + t, sim, C.c_void_p(stream_buf.value + (W + t) * tick_bytes)))
+    def timed(t0_, t1_, step):
+        """ticks [t0_, t1_) on the clock, through step(t, t_end) -> launches: one region per run of ticks the stream buffer
+        holds (barrier before, HIP events and a synchronisation after; the buffer is refilled between regions, off the
+        clock).  Returns the launches and, per region, (ticks, wall s, event ms)."""
+        n_l, regs = 0, []
+        t = t0_
+        while t < t1_:
+            t_end = min(t1_, buffered_until(t))
             barrier()
             tr0 = time.perf_counter()
             eng._check(api.timer_start(h))
-            run_ticks(W, W + K)
+            n_l += step(t, t_end)
             ev_r = C.c_float(0)
-            eng._check(api.timer_stop(h, C.byref(ev_r)))
+            eng._check(api.timer_stop(h, C.byref(ev_r)))  # HIP events on the engine's stream (synchronises it)
             torch.cuda.synchronize()
-            regions.append((time.perf_counter() - tr0, ev_r.value))
-            barrier()
-            ticks_done += K
-        if n_more:
-            c1 = eng.counters()
-            decisions = c1["decisions"] - c0["decisions"]
-    if world > 1:  # MAX over ranks, region by region
-        tr = torch.tensor(regions, dtype=torch.float64, device=red_dev)
+            regs.append((t_end - t, time.perf_counter() - tr0, ev_r.value))
+            t = t_end
+        return n_l, regs
+
+    # exactly K timed steps: one region when the stream buffer holds all W + K ticks, else one per buffer fill, the clock
+    # stopped while the buffer is refilled (this rank's K steps are the sum of its regions; MAX over ranks below)
+    n_launches, regions = timed(W, W + K, run_ticks)
+    barrier()
+    c1 = eng.counters()
+    decisions = c1["decisions"] - c0["decisions"]
+    ticks_done = W + K
+    wall_own, ev_own = sum(r[1] for r in regions), sum(r[2] for r in regions)
+    if world > 1:  # MAX over ranks, region by region and of the totals
+        tr = torch.tensor([list(r) for r in regions] + [[K, wall_own, ev_own]], dtype=torch.float64, device=red_dev)
         dist.all_reduce(tr, op=dist.ReduceOp.MAX)
         regions_all = [tuple(x) for x in tr.tolist()]
+        wall, ev_ms = regions_all[-1][1], C.c_float(regions_all[-1][2])
+        regions_all = regions_all[:-1]
     else:
         regions_all = regions
-    order = sorted(range(len(regions_all)), key=lambda i: regions_all[i][0])
-    mid = order[(len(order) - 1) // 2]
-    wall_own, ev_own = regions[mid]  # this rank's figures of the region that is the job's median
-    wall, ev_ms = regions_all[mid][0], C.c_float(regions_all[mid][1])
+        wall, ev_ms = wall_own, C.c_float(ev_own)
+    # what the timed path computed in its last step, before anything else steps the engine
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, extra={"counters_timed": np.array(
+            [c1[k] - c0[k] for k in ("commands", "decisions", "dense_group_steps", "launches")], dtype=np.float64)})
     # parity property at full size (closed form of the steady-state stream, mode 0):
     # after T ticks every leader has head == T and commit == T-1, no faults.
     if args.mode == 0 and not args.failures:
@@ -1432,18 +1495,18 @@ def main():
     batched = None
     if T == 1 and not args.failures and args.mode == 0 and K >= 32:
         TB = 16
-        for t in range(K):  # the next K ticks into the buffer slots of W .. W+K-1
-            eng._check(api.synth_fill_acks_device(h, 0, ticks_done + t, sim,
-                                                  C.c_void_p(stream_buf.value + (W + t) * tick_bytes)))
+
+        def step_batched(t0_, t1_):
+            t = t0_
+            while t < t1_:
+                n = min(TB, t1_ - t)
+                eng._check(api.step_dense_acks_device_n(h, C.c_void_p(stream_buf.value + (t - stream["base"]) * tick_bytes), n))
+                t += n
+            return 0
+
+        _, regs_b = timed(ticks_done, ticks_done + K, step_batched)
         barrier()
-        tb0 = time.perf_counter()
-        t = 0
-        while t < K:
-            n = min(TB, K - t)
-            eng._check(api.step_dense_acks_device_n(h, C.c_void_p(stream_buf.value + (W + t) * tick_bytes), n))
-            t += n
-        barrier()
-        wall_b = time.perf_counter() - tb0
+        wall_b = sum(r[1] for r in regs_b)
         head, commit = eng.read("head"), eng.read("commit")
         assert (head == ticks_done + K).all() and (commit == ticks_done + K - 1).all(), "closed form violated (batched ticks)"
         dec_b = float(eng.counters()["decisions"] - c1["decisions"])
@@ -1458,7 +1521,6 @@ def main():
                    "bytes_moved_per_group_step": 8 * R + 28 / TB,
                    "note": "same results bit for bit; state read/written once per launch"}
 
-    decisions = decisions / len(regions)  # (every region takes the same decisions: K steps of the same stream)
     per_rank = None
     if world > 1:
         td = torch.tensor([float(decisions)], dtype=torch.float64, device=red_dev)
@@ -1497,12 +1559,11 @@ def main():
                 "parallelism": f"{world} independent shard(s), no collective", **devices_config(args, world),
             },
             "group_steps_per_s": G * world * K / wall,
-            "timed_regions": {"n": len(regions_all), "reported": "median" if len(regions_all) > 1 else "the one region",
-                              "ms_per_step_each": [r[0] * 1e3 / K for r in regions_all],
-                              "ms_per_step_events_each": [r[1] / K for r in regions_all],
-                              "why": "K steps take less than 50 ms: the region is repeated over the following ticks of the stream and "
-                                     "the median is reported (a region's first launch and last wake-up cost ~45 us whatever K is)"
-                                     if len(regions_all) > 1 else None},
+            "timed_regions": {"n": len(regions_all), "steps_each": [int(r[0]) for r in regions_all],
+                              "ms_each": [r[1] * 1e3 for r in regions_all], "ms_events_each": [r[2] for r in regions_all],
+                              "stream_buffer_ticks": S,
+                              "why": "the stream buffer holds fewer than W + K ticks: it is refilled between regions, off the clock, "
+                                     "and ms_per_step is the regions' time over the K steps" if len(regions_all) > 1 else None},
             "per_rank": per_rank,
             "roofline": {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",

@@ -2,8 +2,9 @@
 streams, the dense halves over random mailboxes and the node step under its adversarial traffic, seed after seed, both
 ways of serving the dense halves, for as many seconds as asked:  python tests/soak_host_compiled.py 600
 Not collected by pytest (minutes, not seconds); round 4: 572 seeds x 2 modes in 600 s, no divergence."""
-import sys, time, numpy as np
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys, time, numpy as np
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, HERE)
 from josefine_amd import capi
 from fuzz import random_batch, random_batch_aware
 from host_compiled import HostCompiled
