@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 9u /* v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 10u /* v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -274,6 +274,41 @@ typedef struct jg_engine jg_engine;
  * at now = 0.  Fails with JG_EDEVICE when no gfx950 device / HIP runtime is usable. */
 int jg_engine_create(const jg_config* cfg, jg_engine** out);
 void jg_engine_destroy(jg_engine* e);
+
+/* ---- startup on persisted trees (ABI v10) ---------------------------------------------------------
+ * What a josefine broker does when its process starts: Raft::<Follower>::new for every partition,
+ * which calls Chain::new on the sled tree the previous process left in config.data_directory
+ * (src/raft/follower.rs:68-95, src/raft/chain.rs:117-137).  The image is a sled scan, verbatim, in
+ * host memory: group g0 + i owns the blocks off[i] .. off[i + 1] - 1 (the CSR shape of
+ * jg_chain_compact), ids STRICTLY ascending within a group (sled's order of the 8-byte big-endian
+ * keys = numeric order), and the value of its "commit" key where has_commit[i] is 1.  Payloads stay
+ * on the host.  Per group of the range:
+ *   - its id set and parent pointers become exactly the image's blocks, its commit-key bit has_commit[i];
+ *   - then what a JG_CMD_RESTART row does: Follower, term 0, no vote, no leader, empty queue, votes
+ *     cleared, heartbeat_time 0; Chain::new (Q8): commit = head = id_gen = c (c = the commit key's
+ *     value, else 0; c == 0 re-inserts genesis and id_gen is 1); the election timer re-armed at
+ *     now_ms with the group's next RNG draw; the sticky fault cleared;
+ *   - engine-domain limits become the group's sticky fault (jg_drain_faults), as a restart's would:
+ *     more than JG_CHAIN_WINDOW segments besides the run, or a stored block 0 whose next is not 0
+ *     (genesis' parent is implicit): JG_FAULT_ENGINE_WINDOW_OVERFLOW.
+ * Groups outside [g0, g0 + n) are untouched: a fresh engine followed by a load of [0, G) is a process
+ * that started on those trees.  The chains are held in the canonical form jg_chain_normalize leaves
+ * (the run from genesis, each further segment a maximal stretch with next == id - 1), so the dense
+ * paths take loaded groups as they take built ones.  JG_EINVAL, and nothing changes, for a malformed
+ * image (off[0] != 0, off not monotone, the range outside G, ids not strictly ascending within a
+ * group), for commands submitted and not yet stepped, and while kept node steps (JG_NODE_KEEP) are
+ * outstanding.  A multi-device handle splits the range by group_lo; each shard loads its part on its
+ * own device.  Loading into an engine that is a node of a jg_dense_cluster between rounds is the
+ * caller's responsibility (the cluster's other nodes are not told). */
+typedef struct jg_chain_image {
+  uint32_t g0, n;             /* local groups [g0, g0 + n)                                     */
+  const uint64_t* off;        /* [n + 1] CSR offsets into the block arrays, off[0] == 0         */
+  const uint64_t* blk_id;     /* ids of group g0 + i: off[i] .. off[i + 1] - 1, strictly ascending */
+  const uint64_t* blk_next;   /* Block.next of each                                             */
+  const uint64_t* commit;     /* [n] value of the "commit" key (ignored where absent)           */
+  const uint8_t* has_commit;  /* [n] 1 = the tree has a "commit" key                            */
+} jg_chain_image;
+int jg_engine_load_chains(jg_engine* e, uint64_t now_ms, const jg_chain_image* img);
 
 /* ---- shards of a multi-device engine ------------------------------------------------------------
  * Everything that takes HOST memory works on the parent handle exactly as on a single-device

@@ -25,6 +25,7 @@
 #include "jg_route.h"
 #include "jg_follower.h"
 #include "jg_node.h"
+#include "jg_load.h"
 
 // The host side, by entry-point family (ONE translation unit: the pieces see each other's internals, in this order)
 #include "jg_api_core.h"
@@ -34,3 +35,4 @@
 #include "jg_api_cluster.h"
 #include "jg_api_routed.h"
 #include "jg_api_misc.h"
+#include "jg_api_load.h"

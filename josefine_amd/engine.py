@@ -604,6 +604,38 @@ class BatchedRaft:
                                            nexts.ctypes.data, commits.ctypes.data, removed.ctypes.data))
         return [removed[int(off[i]):int(off[i + 1])].copy() for i in range(len(trees))]
 
+    def load_chains(self, trees=None, now_ms: int = 0, g0: int = 0, *, off=None, blk_id=None, blk_next=None,
+                    commit=None, has_commit=None) -> None:
+        """jg_engine_load_chains: groups g0, g0 + 1, ... restart on the persisted trees given - Raft::<Follower>::new +
+        Chain::new on each (follower.rs:68-95, chain.rs:117-137).  Either `trees` = [(blocks [(id, next), ...] in
+        ascending id order, commit key value or None), ...] one per group, or the CSR arrays directly (off [n + 1],
+        blk_id / blk_next [off[n]], commit [n], has_commit [n])."""
+        self._flush_pending()
+        if trees is not None:
+            trees = list(trees)
+            n = len(trees)
+            off = np.zeros(n + 1, np.uint64)
+            off[1:] = np.cumsum([len(t[0]) for t in trees], dtype=np.uint64) if n else []
+            rows = [b for t in trees for b in t[0]]
+            blk_id = np.array([b[0] for b in rows], dtype=np.uint64)
+            blk_next = np.array([b[1] for b in rows], dtype=np.uint64)
+            commit = np.array([0 if t[1] is None else t[1] for t in trees], dtype=np.uint64)
+            has_commit = np.array([t[1] is not None for t in trees], dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = len(off) - 1
+        blk_id = np.ascontiguousarray(blk_id if blk_id is not None else [], dtype=np.uint64)
+        blk_next = np.ascontiguousarray(blk_next if blk_next is not None else [], dtype=np.uint64)
+        commit = np.ascontiguousarray(commit if commit is not None else np.zeros(n), dtype=np.uint64)
+        has_commit = np.ascontiguousarray(has_commit if has_commit is not None else np.zeros(n), dtype=np.uint8)
+        assert n >= 0 and len(commit) == n and len(has_commit) == n and len(blk_id) == len(blk_next)
+        img = capi.ChainImage()
+        img.g0, img.n = int(g0), n
+        img.off, img.blk_id, img.blk_next = off.ctypes.data, blk_id.ctypes.data, blk_next.ctypes.data
+        img.commit, img.has_commit = commit.ctypes.data, has_commit.ctypes.data
+        if not hasattr(self.api, "engine_load_chains"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_load_chains")
+        self._check(self.api.engine_load_chains(self._h, int(now_ms), C.byref(img)))
+
     def chain_compact_resident(self) -> np.ndarray:
         """jg_chain_compact_resident + jg_drain_compacted: Chain::compact on every healthy group's own
         chain; returns the removed blocks as (group, id) rows, group ascending, ids in walk order."""

@@ -22,6 +22,7 @@
 #include <deque>
 #include <functional>
 #include <map>
+#include <memory>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -146,6 +147,39 @@ class BatchedRaft {
     c.flags = flags;
     check(jg_engine_create(&c, &e_));
     for (auto& s : stores_) s.insert(Block{0, 0, {}});  // genesis (chain.rs:139-153)
+  }
+  // A process that starts on the sled trees its predecessor left (Raft::<Follower>::new -> Chain::new on each,
+  // follower.rs:68-95, chain.rs:117-137): stores[g] is partition g's tree (e.g. ChainStore::from_raw of what is on disk).
+  // Each tree is scanned in key order - 8-byte keys are big-endian block ids, their values decoded Blocks, the "commit"
+  // key read - into one jg_engine_load_chains image; the stores are adopted, so that later restarts, pumps and appends
+  // write to them.  (jg_engine_load_chains is ABI v10: only callers of open() need a library that has it.)
+  static std::unique_ptr<BatchedRaft> open(std::vector<NodeId> node_ids, std::vector<BlockStore> stores, uint64_t now_ms = 0,
+                                           int device = 0, uint64_t seed = 0, uint32_t flags = 0, std::vector<int> devices = {},
+                                           const uint8_t* self_slots = nullptr) {
+    const uint32_t G = (uint32_t)stores.size();
+    std::unique_ptr<BatchedRaft> r(new BatchedRaft(G, std::move(node_ids), device, seed, flags, std::move(devices)));
+    if (self_slots) r->check(jg_set_self_slots(r->e_, self_slots));
+    std::vector<uint64_t> off(1, 0), ids, nexts, commit(G, 0);
+    std::vector<uint8_t> has(G, 0);
+    for (uint32_t g = 0; g < G; g++) {
+      for (const auto& kv : stores[g].raw()) {
+        if (kv.first == formats::ChainStore::commit_key()) {
+          commit[g] = formats::key_block_id(kv.second);
+          has[g] = 1;
+        } else if (kv.first.size() == 8) {
+          ids.push_back(formats::key_block_id(kv.first));
+          nexts.push_back(formats::decode_block(kv.second).next);
+        }
+      }
+      off.push_back(ids.size());
+    }
+    jg_chain_image img{};
+    img.g0 = 0, img.n = G;
+    img.off = off.data(), img.blk_id = ids.data(), img.blk_next = nexts.data(), img.commit = commit.data(), img.has_commit = has.data();
+    r->check(jg_engine_load_chains(r->e_, now_ms, &img));
+    r->stores_ = std::move(stores);
+    for (uint32_t g = 0; g < G; g++) r->stores_[g].reopen();  // Chain::new's genesis where the tree has no commit key (as restart())
+    return r;
   }
   ~BatchedRaft() { jg_engine_destroy(e_); }
   BatchedRaft(const BatchedRaft&) = delete;
