@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 10u /* v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 11u /* v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -309,6 +309,41 @@ typedef struct jg_chain_image {
   const uint8_t* has_commit;  /* [n] 1 = the tree has a "commit" key                            */
 } jg_chain_image;
 int jg_engine_load_chains(jg_engine* e, uint64_t now_ms, const jg_chain_image* img);
+
+/* ---- reading the trees back (ABI v11) --------------------------------------------------------------
+ * The inverse of jg_engine_load_chains: what a sled scan of each group's tree would return, written
+ * in host memory in the image's own CSR shape - group g0 + i owns the rows off[i] .. off[i + 1] - 1,
+ * ids strictly ascending (sled's key order), each with its Block.next, and the value of its "commit"
+ * key where has_commit[i] is 1 (commit[i] is 0 where the key is absent).  With from == NULL every
+ * output but fault[] is exactly a jg_chain_image: loading it into a fresh engine gives each group
+ * what a JG_CMD_RESTART row does on the original.  With from != NULL group g0 + i reports only the
+ * block keys >= from[i] (Chain::range(from..), src/raft/chain.rs:208-228); the commit key is always
+ * reported.  Per group:
+ *   - the chain is decoded from whatever form it is held in (the implicit run of RUN / FAST chains,
+ *     no run under JGF_NO_GENESIS, window segments in any order, a leader's lag-packed commit);
+ *   - fault[i] is the group's sticky fault code.  Below 128 the reference panicked: the tree is
+ *     reported as it stood at the panic.  From 128 on (engine-domain limits, e.g.
+ *     JG_FAULT_ENGINE_WINDOW_OVERFLOW) the image is no longer the tree: the group reports 0 rows
+ *     and has_commit[i] = 0.
+ * The read changes nothing and reflects every step issued before it (JG_NODE_ASYNC steps are
+ * settled first); commands submitted and not yet stepped are not in it.  JG_EINVAL for the range
+ * outside G, a null argument, and while kept node steps (JG_NODE_KEEP) are outstanding.  *n_rows is
+ * set to the number of rows; if it exceeds cap the call returns JG_ECAPACITY and writes nothing else
+ * (cap = 0 with blk_id = blk_next = NULL is the sizing call).  Reading a node of a jg_dense_cluster
+ * between rounds is allowed.  A multi-device handle sizes every shard before any output is
+ * written, then concatenates the shards' parts. */
+typedef struct jg_chain_read {
+  uint32_t g0, n;           /* local groups [g0, g0 + n)                                          */
+  const uint64_t* from;     /* [n] or NULL: rows are the block keys >= from[i]; NULL = the whole tree */
+  uint64_t cap;             /* rows blk_id / blk_next can hold                                    */
+  uint64_t* off;            /* [n + 1] out, off[0] == 0                                           */
+  uint64_t* blk_id;         /* [cap] out: ids of group g0 + i at off[i] .. off[i + 1] - 1, ascending */
+  uint64_t* blk_next;       /* [cap] out: Block.next of each                                      */
+  uint64_t* commit;         /* [n] out: value of the "commit" key (0 where absent)                */
+  uint8_t* has_commit;      /* [n] out                                                            */
+  uint8_t* fault;           /* [n] out: the group's sticky fault code                             */
+} jg_chain_read;
+int jg_engine_read_chains(jg_engine* e, jg_chain_read* r, uint64_t* n_rows);
 
 /* ---- shards of a multi-device engine ------------------------------------------------------------
  * Everything that takes HOST memory works on the parent handle exactly as on a single-device

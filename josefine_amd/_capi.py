@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -164,6 +164,12 @@ class ChainImage(C.Structure):
                 ("blk_next", C.c_void_p), ("commit", C.c_void_p), ("has_commit", C.c_void_p)]
 
 
+class ChainRead(C.Structure):
+    _fields_ = [("g0", C.c_uint32), ("n", C.c_uint32), ("from_", C.c_void_p), ("cap", C.c_uint64), ("off", C.c_void_p),
+                ("blk_id", C.c_void_p), ("blk_next", C.c_void_p), ("commit", C.c_void_p), ("has_commit", C.c_void_p),
+                ("fault", C.c_void_p)]
+
+
 # mailbox words (josefine_gpu.h: JG_ANSWER / JG_AE)
 MAILBOX_NONE = (1 << 56) - 1
 
@@ -271,6 +277,7 @@ class Api:
         "kernel_timing": (C.c_int, [_P, C.c_int]),
         "kernel_timing_read": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
         "engine_load_chains": (C.c_int, [_P, C.c_uint64, C.POINTER(ChainImage)]),
+        "engine_read_chains": (C.c_int, [_P, C.POINTER(ChainRead), C.POINTER(C.c_uint64)]),
     }
     # only the oracle has these
     _ORACLE_PROTOS = {
@@ -312,5 +319,5 @@ HEADER_SYMBOLS = [
     "jg_device_alloc", "jg_device_free", "jg_device_upload", "jg_device_download",
     "jg_timer_start", "jg_timer_stop", "jg_synth_fill_acks_device", "jg_calibrate_stream", "jg_dense_cluster_create", "jg_dense_cluster_destroy", "jg_dense_cluster_set_option", "jg_dense_cluster_set_appends", "jg_dense_cluster_withdraw_appends", "jg_dense_cluster_offer_appends", "jg_dense_cluster_rounds", "jg_dense_cluster_mailboxes", "jg_dense_cluster_round_routed", "jg_kernel_timing", "jg_kernel_timing_read", "jg_last_error", "jg_abi_version",
     "jg_step_node", "jg_node_outbox_view", "jg_submit_reserve", "jg_submit_commit", "jg_node_inbox_columns",
-    "jg_engine_load_chains",
+    "jg_engine_load_chains", "jg_engine_read_chains",
 ]

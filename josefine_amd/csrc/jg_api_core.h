@@ -268,6 +268,14 @@ struct jg_engine {
   }* drain_thread = nullptr;
   hipStream_t copy_stream = nullptr;
   hipEvent_t ev_steps = nullptr, ev_scan = nullptr, ev_done = nullptr;
+  // jg_engine_read_chains: the two staging buffers of its row pieces and the stream that copies them out (kept from the
+  // first read on: a read of a large image is not charged an allocation of its staging every time)
+  struct ReadStage {
+    char* buf = nullptr;
+    size_t bytes = 0;
+    hipStream_t cs = nullptr;
+    hipEvent_t ev_k[2]{}, ev_c[2]{};
+  } read_stage;
   // two sets of the device-side fault / exceptional-row queues: kernels append to [cur_set] while
   // the other one is being copied out
   JgFaultRec* fq[2] = {nullptr, nullptr};

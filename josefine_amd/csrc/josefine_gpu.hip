@@ -26,6 +26,7 @@
 #include "jg_follower.h"
 #include "jg_node.h"
 #include "jg_load.h"
+#include "jg_read.h"
 
 // The host side, by entry-point family (ONE translation unit: the pieces see each other's internals, in this order)
 #include "jg_api_core.h"
@@ -36,3 +37,4 @@
 #include "jg_api_routed.h"
 #include "jg_api_misc.h"
 #include "jg_api_load.h"
+#include "jg_api_read.h"

@@ -636,6 +636,48 @@ class BatchedRaft:
             raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_load_chains")
         self._check(self.api.engine_load_chains(self._h, int(now_ms), C.byref(img)))
 
+    def read_chains(self, g0: int = 0, n: Optional[int] = None, from_=None) -> dict:
+        """jg_engine_read_chains: groups g0 .. g0 + n - 1 as a sled scan of each tree (the inverse of load_chains):
+        dict of off [n + 1], blk_id / blk_next [off[n]] (ids ascending within a group), commit [n], has_commit [n] and
+        fault [n].  `from_` [n]: only the block keys >= from_[i] (Chain::range(from..)).  Sized first, then read."""
+        n = self.G - g0 if n is None else int(n)
+        if not hasattr(self.api, "engine_read_chains"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_read_chains")
+        fr = None if from_ is None else np.ascontiguousarray(from_, dtype=np.uint64)
+        assert fr is None or len(fr) == n
+        out = dict(off=np.zeros(n + 1, np.uint64), commit=np.zeros(n, np.uint64), has_commit=np.zeros(n, np.uint8),
+                   fault=np.zeros(n, np.uint8))
+        r = capi.ChainRead()
+        r.g0, r.n = int(g0), n
+        r.from_ = 0 if fr is None else fr.ctypes.data
+        r.off, r.commit = out["off"].ctypes.data, out["commit"].ctypes.data
+        r.has_commit, r.fault = out["has_commit"].ctypes.data, out["fault"].ctypes.data
+        rows = C.c_uint64(0)
+        rc = self.api.engine_read_chains(self._h, C.byref(r), C.byref(rows))  # the sizing call (cap 0)
+        if rc == capi.ECAPACITY:
+            out["blk_id"] = np.zeros(rows.value, np.uint64)
+            out["blk_next"] = np.zeros(rows.value, np.uint64)
+            r.cap, r.blk_id, r.blk_next = rows.value, out["blk_id"].ctypes.data, out["blk_next"].ctypes.data
+            rc = self.api.engine_read_chains(self._h, C.byref(r), C.byref(rows))
+        else:
+            out["blk_id"], out["blk_next"] = np.zeros(0, np.uint64), np.zeros(0, np.uint64)
+        self._check(rc)
+        return out
+
+    def read_trees(self, g0: int = 0, n: Optional[int] = None, from_=None) -> list:
+        """read_chains in the form load_chains(trees=...) takes: [(blocks [(id, next), ...], commit key value or None),
+        ...] one per group; None for a group whose sticky fault is engine-domain (>= 128: its image is not its tree)."""
+        r = self.read_chains(g0, n, from_)
+        off, ids, nxt = r["off"].astype(np.int64), r["blk_id"].tolist(), r["blk_next"].tolist()
+        out = []
+        for i in range(len(r["commit"])):
+            if r["fault"][i] >= 128:
+                out.append(None)
+                continue
+            blocks = list(zip(ids[off[i]:off[i + 1]], nxt[off[i]:off[i + 1]]))
+            out.append((blocks, int(r["commit"][i]) if r["has_commit"][i] else None))
+        return out
+
     def chain_compact_resident(self) -> np.ndarray:
         """jg_chain_compact_resident + jg_drain_compacted: Chain::compact on every healthy group's own
         chain; returns the removed blocks as (group, id) rows, group ascending, ids in walk order."""

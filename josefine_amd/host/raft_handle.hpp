@@ -181,6 +181,29 @@ class BatchedRaft {
     for (uint32_t g = 0; g < G; g++) r->stores_[g].reopen();  // Chain::new's genesis where the tree has no commit key (as restart())
     return r;
   }
+  // The engine's chain trees read back out (jg_engine_read_chains, ABI v11; only callers need a library that has it): groups
+  // [g0, g0 + n) as the CSR rows of a sled scan of each - what BatchedRaft::open takes, and what stores_[g] must hold.
+  struct ChainRows {
+    std::vector<uint64_t> off, id, next, commit;  // off [n + 1]; id / next [off[n]], ascending per group; commit [n]
+    std::vector<uint8_t> has_commit, fault;       // [n]; fault >= 128: the engine's image is not the tree (no rows)
+  };
+  ChainRows read_chains(uint32_t g0 = 0, uint32_t n = UINT32_MAX) {
+    if (n == UINT32_MAX) n = (uint32_t)stores_.size() - g0;
+    ChainRows c;
+    c.off.assign((size_t)n + 1, 0), c.commit.assign(n, 0), c.has_commit.assign(n, 0), c.fault.assign(n, 0);
+    jg_chain_read r{};
+    r.g0 = g0, r.n = n;
+    r.off = c.off.data(), r.commit = c.commit.data(), r.has_commit = c.has_commit.data(), r.fault = c.fault.data();
+    uint64_t rows = 0;
+    int rc = jg_engine_read_chains(e_, &r, &rows);  // sized first (cap 0) ...
+    if (rc == JG_ECAPACITY) {  // ... then read
+      c.id.resize(rows), c.next.resize(rows);
+      r.cap = rows, r.blk_id = c.id.data(), r.blk_next = c.next.data();
+      rc = jg_engine_read_chains(e_, &r, &rows);
+    }
+    check(rc);
+    return c;
+  }
   ~BatchedRaft() { jg_engine_destroy(e_); }
   BatchedRaft(const BatchedRaft&) = delete;
   BatchedRaft& operator=(const BatchedRaft&) = delete;
