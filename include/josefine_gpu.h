@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 11u /* v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 12u /* v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -344,6 +344,69 @@ typedef struct jg_chain_read {
   uint8_t* fault;           /* [n] out: the group's sticky fault code                             */
 } jg_chain_read;
 int jg_engine_read_chains(jg_engine* e, jg_chain_read* r, uint64_t* n_rows);
+
+/* ---- handing live groups over (ABI v12) -----------------------------------------------------------
+ * A lossless hand-over of groups between engines of ONE node (another device of the process, another
+ * process on the same broker): jg_engine_export_groups writes a full-fidelity state image of local
+ * groups [g0, g0 + n) - a header plus one fixed-stride record per group holding every column the
+ * group's behaviour depends on (term, chain, commit, progress, timers, votes, role, fault; the layout
+ * is DESIGN.md "Handing groups over") - and jg_engine_import_groups makes local groups
+ * [g0, g0 + n) of another engine continue them bit for bit: no restart, no election.  Unlike
+ * jg_engine_load_chains(jg_engine_read_chains(...)) the group keeps its leadership, its vote, its
+ * replication progress and its election timer.
+ *   - records live in host memory, or with JG_MOVE_DEVICE in device memory of the engine's own device
+ *     (jg_device_alloc: 16-byte aligned); a multi-device parent handle takes the host form only.
+ *   - the export changes nothing (JG_NODE_ASYNC steps are settled first, kept node steps refuse).
+ *     With cap_bytes < n * record_bytes it fills the header, returns JG_ECAPACITY and writes nothing
+ *     else (cap_bytes = 0 with records = NULL is the sizing call).  Output rows the groups already
+ *     produced stay in the source's drains; the caller stops driving the source groups once they are
+ *     handed over (not enforced).
+ *   - the import adds shift_ms (wrapping u64) to every election_time and heartbeat_time: a destination
+ *     driven at now + shift_ms decides as the source at now.  Future election timeouts are drawn under
+ *     the destination's seed and global id (group_base + local; the draw count travels).
+ *   - the import refuses with JG_EINVAL and writes nothing for: a range outside G or a null argument;
+ *     a format or record_bytes mismatch; n_replicas, node_ids or the JG_CFG_SEPARATE_COMMIT_KEY bit
+ *     differing from the destination's; queued commands; kept node steps; any record whose check word
+ *     fails or whose fields are out of range (role, own slot >= R, window count > JG_CHAIN_WINDOW) -
+ *     every record is validated on the device before the pass that writes (which also asserts that no
+ *     per-step deferral state of the destination groups is pending: JG_EDEVICE if it is).  An imported group that
+ *     carries a sticky fault writes no fault row (the source reported it).  Importing into a node of a
+ *     jg_dense_cluster between rounds is allowed; the cluster's mailboxes are the caller's business.
+ *   - extra device memory: a host-form export stages through two buffers of at most 2^18 records each
+ *     (kept by the engine, shared with jg_engine_read_chains); a host-form import uploads the whole
+ *     image first: n * record_bytes of scratch for the call.
+ *   - a multi-device handle splits both calls by shard; an import checks every shard's refusals and
+ *     validates every shard's records before any shard writes. */
+#define JG_MOVE_FORMAT 1u  /* jg_group_image_header.format                                          */
+#define JG_MOVE_DEVICE 1u  /* flags: the records are in device memory of the engine's device     */
+typedef struct jg_group_image_header {
+  uint32_t format;                    /* JG_MOVE_FORMAT                                       */
+  uint32_t record_bytes;              /* stride of a record: a multiple of 64, fixed by R     */
+  uint32_t n;                         /* records                                              */
+  uint32_t n_replicas;                /* R of the source                                      */
+  uint32_t node_ids[JG_MAX_REPLICAS]; /* the source's slots (must mean the same nodes)        */
+  uint32_t separate_commit_key;       /* the source's JG_CFG_SEPARATE_COMMIT_KEY bit (0 / 1)   */
+  uint32_t reserved;
+  uint64_t seed;                      /* for information: the source's seed ...               */
+  uint64_t global0;                   /* ... and the global id (group_base + local) of record 0 */
+} jg_group_image_header;
+typedef struct jg_group_export {
+  uint32_t g0, n;                     /* local groups [g0, g0 + n)                            */
+  uint32_t flags;                     /* JG_MOVE_DEVICE or 0                                  */
+  uint32_t reserved;
+  uint64_t cap_bytes;                 /* bytes `records` can hold                             */
+  void* records;                      /* out: n records of header.record_bytes                */
+  jg_group_image_header header;       /* out                                                  */
+} jg_group_export;
+typedef struct jg_group_import {
+  uint32_t g0;                        /* the records land at local groups [g0, g0 + header.n) */
+  uint32_t flags;                     /* JG_MOVE_DEVICE or 0                                  */
+  int64_t shift_ms;                   /* added (wrapping) to election_time and heartbeat_time */
+  const void* records;                /* header.n records                                     */
+  jg_group_image_header header;       /* as the export wrote it                               */
+} jg_group_import;
+int jg_engine_export_groups(jg_engine* e, jg_group_export* x);
+int jg_engine_import_groups(jg_engine* e, const jg_group_import* x);
 
 /* ---- shards of a multi-device engine ------------------------------------------------------------
  * Everything that takes HOST memory works on the parent handle exactly as on a single-device

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -170,6 +170,26 @@ class ChainRead(C.Structure):
                 ("fault", C.c_void_p)]
 
 
+MOVE_FORMAT = 1
+MOVE_DEVICE = 1
+
+
+class GroupImageHeader(C.Structure):
+    _fields_ = [("format", C.c_uint32), ("record_bytes", C.c_uint32), ("n", C.c_uint32), ("n_replicas", C.c_uint32),
+                ("node_ids", C.c_uint32 * MAX_REPLICAS), ("separate_commit_key", C.c_uint32), ("reserved", C.c_uint32),
+                ("seed", C.c_uint64), ("global0", C.c_uint64)]
+
+
+class GroupExport(C.Structure):
+    _fields_ = [("g0", C.c_uint32), ("n", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("cap_bytes", C.c_uint64), ("records", C.c_void_p), ("header", GroupImageHeader)]
+
+
+class GroupImport(C.Structure):
+    _fields_ = [("g0", C.c_uint32), ("flags", C.c_uint32), ("shift_ms", C.c_int64), ("records", C.c_void_p),
+                ("header", GroupImageHeader)]
+
+
 # mailbox words (josefine_gpu.h: JG_ANSWER / JG_AE)
 MAILBOX_NONE = (1 << 56) - 1
 
@@ -278,6 +298,8 @@ class Api:
         "kernel_timing_read": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
         "engine_load_chains": (C.c_int, [_P, C.c_uint64, C.POINTER(ChainImage)]),
         "engine_read_chains": (C.c_int, [_P, C.POINTER(ChainRead), C.POINTER(C.c_uint64)]),
+        "engine_export_groups": (C.c_int, [_P, C.POINTER(GroupExport)]),
+        "engine_import_groups": (C.c_int, [_P, C.POINTER(GroupImport)]),
     }
     # only the oracle has these
     _ORACLE_PROTOS = {
@@ -319,5 +341,5 @@ HEADER_SYMBOLS = [
     "jg_device_alloc", "jg_device_free", "jg_device_upload", "jg_device_download",
     "jg_timer_start", "jg_timer_stop", "jg_synth_fill_acks_device", "jg_calibrate_stream", "jg_dense_cluster_create", "jg_dense_cluster_destroy", "jg_dense_cluster_set_option", "jg_dense_cluster_set_appends", "jg_dense_cluster_withdraw_appends", "jg_dense_cluster_offer_appends", "jg_dense_cluster_rounds", "jg_dense_cluster_mailboxes", "jg_dense_cluster_round_routed", "jg_kernel_timing", "jg_kernel_timing_read", "jg_last_error", "jg_abi_version",
     "jg_step_node", "jg_node_outbox_view", "jg_submit_reserve", "jg_submit_commit", "jg_node_inbox_columns",
-    "jg_engine_load_chains", "jg_engine_read_chains",
+    "jg_engine_load_chains", "jg_engine_read_chains", "jg_engine_export_groups", "jg_engine_import_groups",
 ]

@@ -27,6 +27,7 @@
 #include "jg_node.h"
 #include "jg_load.h"
 #include "jg_read.h"
+#include "jg_move.h"
 
 // The host side, by entry-point family (ONE translation unit: the pieces see each other's internals, in this order)
 #include "jg_api_core.h"
@@ -38,3 +39,4 @@
 #include "jg_api_misc.h"
 #include "jg_api_load.h"
 #include "jg_api_read.h"
+#include "jg_api_move.h"

@@ -678,6 +678,48 @@ class BatchedRaft:
             out.append((blocks, int(r["commit"][i]) if r["has_commit"][i] else None))
         return out
 
+    def export_groups(self, g0: int = 0, n: Optional[int] = None, device: bool = False) -> "GroupImage":
+        """jg_engine_export_groups: the full state of groups g0 .. g0 + n - 1 as a GroupImage (header fields plus one
+        record per group: numpy uint8 [n, record_bytes], or with `device` a buffer in this engine's device memory).
+        Changes nothing; import_groups on another engine of the same node continues the groups bit for bit."""
+        n = self.G - g0 if n is None else int(n)
+        if not hasattr(self.api, "engine_export_groups"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_export_groups")
+        x = capi.GroupExport()
+        x.g0, x.n, x.flags = int(g0), n, capi.MOVE_DEVICE if device else 0
+        rc = self.api.engine_export_groups(self._h, C.byref(x))  # the sizing call (cap 0): the header
+        if rc != capi.ECAPACITY:
+            self._check(rc)
+        nbytes = n * x.header.record_bytes
+        if device:
+            p = C.c_void_p()
+            self._check(self.api.device_alloc(self._h, max(nbytes, 16), C.byref(p)))
+            img = GroupImage(x.header, g0=int(g0), device_ptr=p, owner=self)
+            x.records = p.value
+        else:
+            img = GroupImage(x.header, g0=int(g0), records=np.zeros((n, x.header.record_bytes), np.uint8))
+            x.records = img.records.ctypes.data
+        x.cap_bytes = nbytes
+        self._check(self.api.engine_export_groups(self._h, C.byref(x)))
+        return img
+
+    def import_groups(self, image: "GroupImage", g0: Optional[int] = None, shift_ms: int = 0) -> None:
+        """jg_engine_import_groups: the image's groups continue at local groups g0 .. g0 + n - 1 (default: the indices
+        they were exported from); `shift_ms` is added (wrapping) to their election and heartbeat times."""
+        if not hasattr(self.api, "engine_import_groups"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_import_groups")
+        self._flush_pending()
+        x = capi.GroupImport()
+        x.g0 = image.g0 if g0 is None else int(g0)
+        x.shift_ms = int(shift_ms)
+        x.header = image.header
+        if image.device_ptr is not None:
+            x.flags, x.records = capi.MOVE_DEVICE, image.device_ptr.value
+        else:
+            rec = np.ascontiguousarray(image.records, dtype=np.uint8)
+            x.records = rec.ctypes.data
+        self._check(self.api.engine_import_groups(self._h, C.byref(x)))
+
     def chain_compact_resident(self) -> np.ndarray:
         """jg_chain_compact_resident + jg_drain_compacted: Chain::compact on every healthy group's own
         chain; returns the removed blocks as (group, id) rows, group ascending, ids in walk order."""
@@ -688,6 +730,48 @@ class BatchedRaft:
 
     def handle(self, group: int) -> "RaftHandle":
         return RaftHandle(self, group)
+
+
+class GroupImage:
+    """A state image of jg_engine_export_groups: the header's fields (format, record_bytes, n, n_replicas, node_ids,
+    separate_commit_key, seed, global0), `g0` (the local index the records were exported from) and the records - a numpy
+    uint8 [n, record_bytes] array, or `device_ptr` in the exporting engine's device memory (freed with the image)."""
+
+    def __init__(self, header, g0: int = 0, records: Optional[np.ndarray] = None, device_ptr=None, owner=None):
+        self.header = capi.GroupImageHeader()
+        C.pointer(self.header)[0] = header
+        self.g0, self.records, self.device_ptr, self._owner = int(g0), records, device_ptr, owner
+        for f, *_ in capi.GroupImageHeader._fields_:
+            if f != "reserved":
+                v = getattr(self.header, f)
+                setattr(self, f, list(v)[:self.header.n_replicas] if f == "node_ids" else int(v))
+
+    def to_host(self) -> np.ndarray:
+        """the records as numpy uint8 [n, record_bytes] (a download of the device form)"""
+        if self.device_ptr is None:
+            return self.records
+        out = np.zeros((self.n, self.record_bytes), np.uint8)
+        if out.nbytes:
+            self._owner._check(self._owner.api.device_download(self._owner._h, out.ctypes.data, self.device_ptr, out.nbytes))
+        return out
+
+    def free(self) -> None:
+        if self.device_ptr is not None and self._owner is not None and getattr(self._owner, "_h", None):
+            self._owner.api.device_free(self._owner._h, self.device_ptr)
+        self.device_ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def move_groups(src: BatchedRaft, dst: BatchedRaft, g0: int, n: int, dst_g0: Optional[int] = None, shift_ms: int = 0) -> None:
+    """Hand groups g0 .. g0 + n - 1 of `src` over to `dst` (at dst_g0, default g0) without a restart: export, import.
+    The caller stops driving them on `src` afterwards."""
+    img = src.export_groups(g0, n)
+    dst.import_groups(img, g0 if dst_g0 is None else dst_g0, shift_ms)
 
 
 class Shard:

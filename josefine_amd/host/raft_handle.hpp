@@ -204,6 +204,50 @@ class BatchedRaft {
     check(rc);
     return c;
   }
+  // Live groups handed over to another BatchedRaft of the same node without a restart (jg_engine_export_groups /
+  // jg_engine_import_groups, ABI v12; only callers need a library that has it): the engine's state image of groups
+  // [g0, g0 + n) plus what the adapter keeps beside it - each group's BlockStore (the sled tree stays the same tree), its
+  // queued client request tokens and the proposals behind them (a follower / candidate forwards them when it learns a
+  // leader: follower.rs:190-197).  Drain this handle's rows first: what the groups already produced stays here.
+  struct GroupImage {
+    jg_group_image_header header{};
+    std::vector<uint8_t> records;        // [n * header.record_bytes]
+    std::vector<BlockStore> stores;      // [n]
+    std::vector<std::deque<uint64_t>> queued;
+    std::vector<std::map<uint64_t, std::vector<uint8_t>>> proposals;  // [n]: request id -> proposal
+  };
+  GroupImage export_groups(uint32_t g0 = 0, uint32_t n = UINT32_MAX) {
+    if (n == UINT32_MAX) n = (uint32_t)stores_.size() - g0;
+    GroupImage im;
+    jg_group_export x{};
+    x.g0 = g0, x.n = n;
+    const int rc = jg_engine_export_groups(e_, &x);  // the sizing call (cap 0): the header
+    if (rc != JG_ECAPACITY) check(rc);
+    im.records.resize((size_t)n * x.header.record_bytes);
+    x.cap_bytes = im.records.size(), x.records = im.records.data();
+    check(jg_engine_export_groups(e_, &x));
+    im.header = x.header;
+    im.stores.assign(stores_.begin() + g0, stores_.begin() + g0 + n);
+    im.queued.assign(queued_.begin() + g0, queued_.begin() + g0 + n);
+    im.proposals.resize(n);
+    for (auto it = pending_reqs_.lower_bound({g0, 0}); it != pending_reqs_.end() && it->first.first < g0 + n; ++it)
+      im.proposals[it->first.first - g0][it->first.second] = it->second;
+    return im;
+  }
+  // the image's groups continue at [g0, g0 + n) of this handle (its timers moved by shift_ms); their stores, queued tokens
+  // and proposals are adopted (whatever these groups held here before is dropped)
+  void import_groups(GroupImage im, uint32_t g0 = 0, int64_t shift_ms = 0) {
+    jg_group_import y{};
+    y.g0 = g0, y.shift_ms = shift_ms, y.header = im.header, y.records = im.records.data();
+    check(jg_engine_import_groups(e_, &y));
+    const uint32_t n = im.header.n;
+    pending_reqs_.erase(pending_reqs_.lower_bound({g0, 0}), pending_reqs_.lower_bound({g0 + n, 0}));  // (what the groups held)
+    for (uint32_t i = 0; i < n; i++) {
+      stores_[g0 + i] = std::move(im.stores[i]);
+      queued_[g0 + i] = std::move(im.queued[i]);
+      for (auto& kv : im.proposals[i]) pending_reqs_[{g0 + i, kv.first}] = std::move(kv.second);
+    }
+  }
   ~BatchedRaft() { jg_engine_destroy(e_); }
   BatchedRaft(const BatchedRaft&) = delete;
   BatchedRaft& operator=(const BatchedRaft&) = delete;

@@ -1,7 +1,7 @@
 #!/bin/bash
 # jg_engine_read_chains at 1 M groups x 64 blocks, R = 5: the timed run, then the same run under rocprofv3 (kernel and
 # memory-copy traces), summarised into profiles/r07/read_chains_1m_x_64.txt's table.  Each GPU step has its own time limit.
-set -eu
+set -euo pipefail  # (a GPU step that fails ends the script: its status is not tee's)
 cd "$(dirname "$0")/../.."
 OUT=${OUT:-$(mktemp -d -t read_chains_1m.XXXXXX)}  # (the traces: give OUT to keep them somewhere else)
 echo "output in $OUT"
