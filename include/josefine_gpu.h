@@ -19,7 +19,8 @@
  *     `jg_last_error()` returns a thread-local description of the last failure;
  *   - reference panics / `Err` returns never abort a batch: they are recorded as
  *     a sticky per-group fault code (`JG_FIELD_FAULT`), after which the group
- *     ignores commands until `JG_CMD_RESTART` (the process would be dead);
+ *     ignores commands until `JG_CMD_RESTART` (the process would be dead) - a
+ *     vacant slot (`JG_FAULT_VACANT`) ignores those too, until it is opened;
  *   - BlockId is the reference's 8-byte big-endian id (src/raft/chain.rs:29-36,
  *     63-67) carried as a native uint64_t (same ordering);
  *   - one engine is externally synchronised (one caller thread at a time),
@@ -35,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 12u /* v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 13u /* v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -142,7 +143,8 @@ enum {
                                              (the first JG_FOREIGN_VOTERS are counted, election.rs:33-35) */
   JG_FAULT_ENGINE_DENSE_NONLEADER = 131,  /* dense tick asked a non-leader group to append         */
   JG_FAULT_ENGINE_DENSE_APPENDS = 132,    /* own slot of a dense ack block >= JG_MAX_DENSE_APPENDS */
-  JG_FAULT_ENGINE_MAILBOX_RANGE = 133     /* a block id >= 2^56 - 1 would have to go into a mailbox word */
+  JG_FAULT_ENGINE_MAILBOX_RANGE = 133,    /* a block id >= 2^56 - 1 would have to go into a mailbox word */
+  JG_FAULT_VACANT = 255                   /* not a fault: the slot hosts no partition (jg_engine_close_groups) */
 };
 
 /* ---- engine configuration ---------------------------------------------------
@@ -181,7 +183,9 @@ enum {
    * accesses per row and pass) instead of binning the rows by tile of 256 partitions and applying a tile's rows to its
    * columns in LDS.  The results are the same bit for bit; the flat passes are the statement the tiled ones are held to
    * (tests/test_node_step.py) and an A/B switch - nothing to set in production. */
-  JG_CFG_FLAT_ROW_PASSES = 2u
+  JG_CFG_FLAT_ROW_PASSES = 2u,
+  /* every slot starts VACANT (jg_engine_open_groups): a broker sizes the engine's capacity, then opens partitions */
+  JG_CFG_START_VACANT = 4u
 };
 
 /* ---- SoA command batch (host memory), SURVEY.md §8(a) a18 -------------------- */
@@ -359,8 +363,8 @@ int jg_engine_read_chains(jg_engine* e, jg_chain_read* r, uint64_t* n_rows);
  *   - the export changes nothing (JG_NODE_ASYNC steps are settled first, kept node steps refuse).
  *     With cap_bytes < n * record_bytes it fills the header, returns JG_ECAPACITY and writes nothing
  *     else (cap_bytes = 0 with records = NULL is the sizing call).  Output rows the groups already
- *     produced stay in the source's drains; the caller stops driving the source groups once they are
- *     handed over (not enforced).
+ *     produced stay in the source's drains; jg_engine_close_groups (ABI v13) then makes the source's
+ *     slots vacant, so that nothing drives them there any more.
  *   - the import adds shift_ms (wrapping u64) to every election_time and heartbeat_time: a destination
  *     driven at now + shift_ms decides as the source at now.  Future election timeouts are drawn under
  *     the destination's seed and global id (group_base + local; the draw count travels).
@@ -407,6 +411,46 @@ typedef struct jg_group_import {
 } jg_group_import;
 int jg_engine_export_groups(jg_engine* e, jg_group_export* x);
 int jg_engine_import_groups(jg_engine* e, const jg_group_import* x);
+
+/* ---- vacant slots: opening and closing partitions at runtime (ABI v13) ------------------------------
+ * A slot is HOSTED (it holds a partition's Raft state) or VACANT (it hosts none).  A vacant slot has no
+ * state that evolves: every command row addressed to it is ignored - JG_CMD_RESTART and JG_CMD_RECREATE
+ * included - it emits no message, fsm or fault row and writes "nothing" into every outbox column, the
+ * dense entry points, compaction and routed rounds leave it alone.  jg_read_state(JG_FIELD_FAULT) reads
+ * JG_FAULT_VACANT, jg_engine_read_chains reads it as no rows and no commit key with that code, and
+ * jg_drain_faults never reports it.  The vacant state is canonical: term 0, no vote, no leader, no
+ * queue, Chain::new's genesis only (commit = head = 0, id_gen = 1), every progress head 0 in Probe,
+ * heartbeat and election time 0 - only the own replica slot and the timeout RNG's draw count are kept,
+ * so a slot closed and reopened never reuses a draw.  export_groups of a vacant slot is that record, and
+ * importing it makes the destination slot vacant.
+ *   - jg_engine_open_groups: every listed slot, which must be vacant, becomes what a JG_CMD_RECREATE row
+ *     applied at now_ms makes of a slot (Raft::<Follower>::new on an empty data directory, the next
+ *     timeout draw under the engine's seed, the slot's global id and its carried draw count); with
+ *     self_slots the own replica slot is set per listed slot.  A partition whose sled tree exists is
+ *     opened by jg_engine_load_chains over its range instead: the load overwrites a vacant slot as it
+ *     overwrites any slot.
+ *   - jg_engine_close_groups: every listed slot, which must be hosted, becomes vacant without emitting
+ *     anything; rows it produced before stay in the drains.
+ *   - both refuse with JG_EINVAL and write nothing for: an index out of range, a list that is not strictly
+ *     ascending, opening a hosted slot or closing a vacant one, self_slots[i] >= R, queued commands, kept
+ *     node steps.  Every entry is checked on the device before the pass that writes.
+ *   - the set: groups == NULL is the range g0 .. g0 + n - 1; else n local indices, strictly ascending, in
+ *     host memory or with JG_GROUPS_DEVICE in the engine's own device memory (a multi-device parent
+ *     handle takes host lists: it splits them by shard, checks every shard, then writes).
+ *   - jg_engine_list_groups: which = JG_LIST_VACANT or JG_LIST_HOSTED over local slots g0 .. g0 + n - 1;
+ *     the first min(cap, total) matching indices, ascending, into `out` (host memory), *total = the number
+ *     of matches (cap 0: the count only). */
+enum { JG_GROUPS_DEVICE = 1u };       /* jg_group_set.flags: groups / self_slots are in the engine's device memory */
+enum { JG_LIST_VACANT = 0u, JG_LIST_HOSTED = 1u };
+typedef struct jg_group_set {
+  uint32_t g0, n;                     /* groups == NULL: the range g0 .. g0 + n - 1                 */
+  const uint32_t* groups;             /* [n] local indices, STRICTLY ascending                      */
+  const uint8_t* self_slots;          /* open only: [n] own slot per listed slot, NULL: keep        */
+  uint32_t flags, reserved;           /* JG_GROUPS_*                                                */
+} jg_group_set;
+int jg_engine_open_groups(jg_engine* e, uint64_t now_ms, const jg_group_set* s);
+int jg_engine_close_groups(jg_engine* e, const jg_group_set* s);
+int jg_engine_list_groups(jg_engine* e, uint32_t which, uint32_t g0, uint32_t n, uint32_t* out, size_t cap, size_t* total);
 
 /* ---- shards of a multi-device engine ------------------------------------------------------------
  * Everything that takes HOST memory works on the parent handle exactly as on a single-device

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -46,9 +46,11 @@ FAULT_ENGINE_FOREIGN_VOTER = 129
 FAULT_ENGINE_DENSE_NONLEADER = 131
 FAULT_ENGINE_DENSE_APPENDS = 132
 FAULT_ENGINE_MAILBOX_RANGE = 133
+FAULT_VACANT = 255  # not a fault: the slot hosts no partition
 
 CFG_SEPARATE_COMMIT_KEY = 1
 CFG_FLAT_ROW_PASSES = 2  # jg_step_node's row passes untiled (the tiled ones' statement; an A/B)
+CFG_START_VACANT = 4  # every slot starts vacant
 NODE_LEADER_HALF, NODE_FOLLOWER_HALF, NODE_TICK, NODE_ASYNC, NODE_COMMON_AE, NODE_FSM_FUSED, NODE_KEEP = 1, 2, 4, 8, 16, 32, 64
 
 FSM_APPLY_LEADER, FSM_APPLY_FOLLOWER, FSM_NOTIFY, FSM_LEADER_STEP = 0, 1, 2, 3
@@ -190,6 +192,16 @@ class GroupImport(C.Structure):
                 ("header", GroupImageHeader)]
 
 
+GROUPS_DEVICE = 1
+LIST_VACANT = 0
+LIST_HOSTED = 1
+
+
+class GroupSet(C.Structure):
+    _fields_ = [("g0", C.c_uint32), ("n", C.c_uint32), ("groups", C.c_void_p), ("self_slots", C.c_void_p),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # mailbox words (josefine_gpu.h: JG_ANSWER / JG_AE)
 MAILBOX_NONE = (1 << 56) - 1
 
@@ -300,6 +312,9 @@ class Api:
         "engine_read_chains": (C.c_int, [_P, C.POINTER(ChainRead), C.POINTER(C.c_uint64)]),
         "engine_export_groups": (C.c_int, [_P, C.POINTER(GroupExport)]),
         "engine_import_groups": (C.c_int, [_P, C.POINTER(GroupImport)]),
+        "engine_open_groups": (C.c_int, [_P, C.c_uint64, C.POINTER(GroupSet)]),
+        "engine_close_groups": (C.c_int, [_P, C.POINTER(GroupSet)]),
+        "engine_list_groups": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     }
     # only the oracle has these
     _ORACLE_PROTOS = {
@@ -342,4 +357,5 @@ HEADER_SYMBOLS = [
     "jg_timer_start", "jg_timer_stop", "jg_synth_fill_acks_device", "jg_calibrate_stream", "jg_dense_cluster_create", "jg_dense_cluster_destroy", "jg_dense_cluster_set_option", "jg_dense_cluster_set_appends", "jg_dense_cluster_withdraw_appends", "jg_dense_cluster_offer_appends", "jg_dense_cluster_rounds", "jg_dense_cluster_mailboxes", "jg_dense_cluster_round_routed", "jg_kernel_timing", "jg_kernel_timing_read", "jg_last_error", "jg_abi_version",
     "jg_step_node", "jg_node_outbox_view", "jg_submit_reserve", "jg_submit_commit", "jg_node_inbox_columns",
     "jg_engine_load_chains", "jg_engine_read_chains", "jg_engine_export_groups", "jg_engine_import_groups",
+    "jg_engine_open_groups", "jg_engine_close_groups", "jg_engine_list_groups",
 ]

@@ -1027,7 +1027,8 @@ template <uint32_t KINDS = JG_KINDS_ALL>
 __device__ inline void jg_apply(const JgDev& d, JgLane& L, const JgCmd& c, const uint64_t* blk_id,
                                 const uint64_t* blk_next) {
   if (JG_KIND_IN(JG_CMD_RESTART) && (c.kind == JG_CMD_RESTART || c.kind == JG_CMD_RECREATE)) {  // (one mask bit for the two)
-    jg_restart(d, L, c.kind == JG_CMD_RECREATE);
+    // a vacant slot hosts no partition: a row addressed to it does not create one (jg_engine_open_groups does)
+    if (jg_fault(L) != JG_FAULT_VACANT) jg_restart(d, L, c.kind == JG_CMD_RECREATE);
     return;
   }
   if (jg_fault(L)) return;  // the reference process is gone

@@ -488,7 +488,13 @@ __global__ void k_init_groups(JgDev d, const uint8_t* __restrict__ self_slots) {
     L.rng_draws = 0;
     uint32_t s = self_slots ? self_slots[g] : 0;
     L.flags = JG_ROLE_FOLLOWER | (s << JGF_SELF_SHIFT);
-    jg_set_election_timeout(d, L);  // follower.rs:93-95 at now = 0
+    if (d.cfg_flags & JG_CFG_START_VACANT) {  // the canonical vacant record (jg_hosting.h: k_groups_close), no draw taken
+      L.flags |= JG_FAULT_VACANT << JGF_FAULT_SHIFT;
+      L.election_time = 0;
+      L.election_timeout = 0;
+    } else {
+      jg_set_election_timeout(d, L);  // follower.rs:93-95 at now = 0
+    }
     d.mlag[g] = 0;  // every progress head 0 = lag 0 below head 0
     jg_store(d, L);
   }

@@ -28,6 +28,7 @@
 #include "jg_load.h"
 #include "jg_read.h"
 #include "jg_move.h"
+#include "jg_hosting.h"
 
 // The host side, by entry-point family (ONE translation unit: the pieces see each other's internals, in this order)
 #include "jg_api_core.h"
@@ -40,3 +41,4 @@
 #include "jg_api_load.h"
 #include "jg_api_read.h"
 #include "jg_api_move.h"
+#include "jg_api_hosting.h"

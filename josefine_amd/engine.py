@@ -154,16 +154,107 @@ def expand_fsm_rows(rows: np.ndarray) -> np.ndarray:
     return out
 
 
-class BatchedRaft:
+class _Hosting:
+    """Vacant slots (ABI v13): open_groups / close_groups / vacant_groups / hosted_groups over an engine handle (a
+    BatchedRaft, or one shard of a multi-device one)."""
+
+    def _group_set(self, groups, self_slots, device: bool, keep: list) -> "capi.GroupSet":
+        s = capi.GroupSet()
+        if isinstance(groups, range) and groups.step == 1 and self_slots is None and not device:
+            s.g0, s.n = (groups.start, len(groups)) if len(groups) else (0, 0)
+            return s
+        g = np.asarray(list(groups) if not isinstance(groups, np.ndarray) else groups, dtype=np.int64).reshape(-1)
+        order = np.argsort(g, kind="stable")
+        g = g[order]
+        if g.size and (g[0] < 0 or g[-1] >= (1 << 32)):
+            raise EngineError(capi.EINVAL, "slot index out of range")
+        if g.size > 1 and (np.diff(g) == 0).any():
+            raise EngineError(capi.EINVAL, "a slot is listed twice")
+        lst = np.ascontiguousarray(g, dtype=np.uint32)
+        own = None
+        if self_slots is not None:
+            own = np.ascontiguousarray(np.asarray(self_slots, dtype=np.int64).reshape(-1)[order], dtype=np.uint8)
+            assert own.shape == lst.shape, "one own slot per listed slot"
+        s.n = lst.size
+        if device:
+            s.flags = capi.GROUPS_DEVICE
+            for a, field in ((lst, "groups"), (own, "self_slots")):
+                if a is None:
+                    continue
+                p = C.c_void_p()
+                self._check(self.api.device_alloc(self._h, max(a.nbytes, 16), C.byref(p)))
+                keep.append(p)
+                if a.nbytes:
+                    self._check(self.api.device_upload(self._h, p, a.ctypes.data, a.nbytes))
+                setattr(s, field, p.value)
+        else:
+            keep += [lst, own]
+            s.groups = lst.ctypes.data
+            s.self_slots = own.ctypes.data if own is not None else None
+        return s
+
+    def _hosting_call(self, fn, groups, self_slots, device, *args) -> None:
+        if hasattr(self, "_flush_pending"):
+            self._flush_pending()
+        keep: list = []
+        try:
+            s = self._group_set(groups, self_slots, device, keep)
+            self._check(fn(self._h, *args, C.byref(s)))
+        finally:
+            for p in keep:
+                if isinstance(p, C.c_void_p):
+                    self.api.device_free(self._h, p)
+
+    def open_groups(self, groups, now_ms: int = 0, self_slots=None, device: bool = False) -> None:
+        """jg_engine_open_groups: every listed slot, which must be vacant, becomes what a JG_CMD_RECREATE row applied at
+        now_ms makes of it.  `groups`: any iterable of slot indices (sorted here; a duplicate is refused) or a range;
+        `self_slots`: the own replica slot per listed slot (in the order given); `device`: pass the list through this
+        engine's device memory (JG_GROUPS_DEVICE)."""
+        self._hosting_call(self.api.engine_open_groups, groups, self_slots, device, int(now_ms))
+
+    def close_groups(self, groups, device: bool = False) -> None:
+        """jg_engine_close_groups: every listed slot, which must host a partition, becomes vacant (the canonical record;
+        the rows it produced before stay in the drains)."""
+        self._hosting_call(self.api.engine_close_groups, groups, None, device)
+
+    def _list(self, which: int, g0: int, n: Optional[int], limit: Optional[int]) -> np.ndarray:
+        n = self.G - int(g0) if n is None else int(n)
+        cap = n if limit is None else max(0, min(int(limit), n))
+        out = np.zeros(max(cap, 1), np.uint32)
+        total = C.c_size_t(0)
+        self._check(self.api.engine_list_groups(self._h, which, int(g0), n, out.ctypes.data, cap, C.byref(total)))
+        return out[:min(cap, total.value)]
+
+    def vacant_groups(self, g0: int = 0, n: Optional[int] = None, limit: Optional[int] = None) -> np.ndarray:
+        """jg_engine_list_groups(JG_LIST_VACANT): the vacant slots of g0 .. g0 + n - 1 ascending (the first `limit`)"""
+        return self._list(capi.LIST_VACANT, g0, n, limit)
+
+    def hosted_groups(self, g0: int = 0, n: Optional[int] = None, limit: Optional[int] = None) -> np.ndarray:
+        """jg_engine_list_groups(JG_LIST_HOSTED): the slots of g0 .. g0 + n - 1 that host a partition, ascending"""
+        return self._list(capi.LIST_HOSTED, g0, n, limit)
+
+    def count_groups(self, vacant: bool = True, g0: int = 0, n: Optional[int] = None) -> int:
+        """the number of vacant (or hosted) slots of g0 .. g0 + n - 1: jg_engine_list_groups with cap 0"""
+        n = self.G - int(g0) if n is None else int(n)
+        total = C.c_size_t(0)
+        which = capi.LIST_VACANT if vacant else capi.LIST_HOSTED
+        self._check(self.api.engine_list_groups(self._h, which, int(g0), n, None, 0, C.byref(total)))
+        return int(total.value)
+
+
+class BatchedRaft(_Hosting):
     """N independent Raft node instances behind one engine handle."""
 
     def __init__(self, n_groups: int, n_replicas: int = 1, node_ids: Optional[Sequence[int]] = None,
                  self_slots: Optional[Sequence[int]] = None, seed: int = 0, device_id: int = 0,
                  group_base: int = 0, flags: int = 0, heartbeat_timeout_ms: int = 100,
                  election_timeout_ms: Tuple[int, int] = (500, 1000), api: Optional[capi.Api] = None,
-                 device_ids: Optional[Sequence[int]] = None):
+                 device_ids: Optional[Sequence[int]] = None, start_vacant: bool = False):
         """`device_ids` (HIP engine only): shard the groups over these devices behind this one
-        handle (contiguous ownership; a device may be listed several times) — jg_config.n_devices."""
+        handle (contiguous ownership; a device may be listed several times) — jg_config.n_devices.
+        `start_vacant`: every slot starts vacant (JG_CFG_START_VACANT); open_groups makes partitions of them."""
+        if start_vacant:
+            flags |= capi.CFG_START_VACANT
         self.api = api if api is not None else device_api()
         self.G, self.R = int(n_groups), int(n_replicas)
         if node_ids is None:
@@ -767,16 +858,23 @@ class GroupImage:
             pass
 
 
-def move_groups(src: BatchedRaft, dst: BatchedRaft, g0: int, n: int, dst_g0: Optional[int] = None, shift_ms: int = 0) -> None:
+def move_groups(src: BatchedRaft, dst: BatchedRaft, g0: int, n: int, dst_g0: Optional[int] = None, shift_ms: int = 0,
+                close_source: bool = False) -> None:
     """Hand groups g0 .. g0 + n - 1 of `src` over to `dst` (at dst_g0, default g0) without a restart: export, import.
-    The caller stops driving them on `src` afterwards."""
+    The caller stops driving them on `src` afterwards - or, with `close_source`, the hosted ones among them are closed on
+    `src` once the import has succeeded (vacant slots: src emits nothing more for them, under any step)."""
     img = src.export_groups(g0, n)
     dst.import_groups(img, g0 if dst_g0 is None else dst_g0, shift_ms)
+    if close_source:
+        hosted = src.hosted_groups(g0, n)
+        if hosted.size:
+            src.close_groups(hosted)
 
 
-class Shard:
+class Shard(_Hosting):
     """One shard of a multi-device BatchedRaft: a borrowed engine handle (owned by the parent)
-    plus the group range it owns.  Quacks enough like a BatchedRaft for the device-pointer calls."""
+    plus the group range it owns.  Quacks enough like a BatchedRaft for the device-pointer calls (open_groups /
+    close_groups with `device`: shard-local indices in the shard's device memory)."""
 
     def __init__(self, parent: BatchedRaft, info: "capi.ShardInfo"):
         self.parent, self.api = parent, parent.api

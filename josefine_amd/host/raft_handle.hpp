@@ -129,9 +129,11 @@ class BatchedRaft {
   // `devices`: shard the groups over these HIP devices behind this one handle (jg_config.n_devices:
   // contiguous ownership, a device may repeat) — one event loop still owns the handle, as in the
   // reference (server.rs:103-165); empty = one shard on `device`.
+  // `start_vacant` (JG_CFG_START_VACANT): every slot starts vacant - a broker sizes the engine, then opens partitions.
   BatchedRaft(uint32_t n_groups, std::vector<NodeId> node_ids, int device = 0, uint64_t seed = 0,
-              uint32_t flags = 0, std::vector<int> devices = {})
+              uint32_t flags = 0, std::vector<int> devices = {}, bool start_vacant = false)
       : stores_(n_groups), queued_(n_groups), ids_(node_ids) {
+    if (start_vacant) flags |= JG_CFG_START_VACANT;
     jg_config c{};
     c.n_devices = (uint32_t)devices.size();
     for (size_t d = 0; d < devices.size() && d < JG_MAX_DEVICES; d++) c.device_ids[d] = devices[d];
@@ -146,7 +148,8 @@ class BatchedRaft {
     c.seed = seed;
     c.flags = flags;
     check(jg_engine_create(&c, &e_));
-    for (auto& s : stores_) s.insert(Block{0, 0, {}});  // genesis (chain.rs:139-153)
+    if (!start_vacant)
+      for (auto& s : stores_) s.insert(Block{0, 0, {}});  // genesis (chain.rs:139-153)
   }
   // A process that starts on the sled trees its predecessor left (Raft::<Follower>::new -> Chain::new on each,
   // follower.rs:68-95, chain.rs:117-137): stores[g] is partition g's tree (e.g. ChainStore::from_raw of what is on disk).
@@ -248,6 +251,41 @@ class BatchedRaft {
       for (auto& kv : im.proposals[i]) pending_reqs_[{g0 + i, kv.first}] = std::move(kv.second);
     }
   }
+  // Partitions opened and closed at runtime (jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, ABI
+  // v13; only callers need a library that has them): LeaderAndIsr creating a replica in a running broker is an open of a
+  // vacant slot - what a JG_CMD_RECREATE row does, with the store reset to Chain::new's genesis; deleting one is a close,
+  // which drops the slot's store, its queued request tokens and their proposals.  A vacant slot ignores every row.
+  void open_groups(const std::vector<uint32_t>& groups, uint64_t now_ms, const std::vector<uint8_t>* self_slots = nullptr) {
+    jg_group_set s{};
+    s.n = (uint32_t)groups.size(), s.groups = groups.data(), s.self_slots = self_slots ? self_slots->data() : nullptr;
+    check(jg_engine_open_groups(e_, now_ms, &s));
+    for (uint32_t g : groups) {
+      stores_[g] = BlockStore{};
+      stores_[g].insert(Block{0, 0, {}});
+      extend_failed_.erase(g);
+    }
+  }
+  void close_groups(const std::vector<uint32_t>& groups) {
+    jg_group_set s{};
+    s.n = (uint32_t)groups.size(), s.groups = groups.data();
+    check(jg_engine_close_groups(e_, &s));
+    for (uint32_t g : groups) {
+      stores_[g] = BlockStore{};
+      queued_[g].clear();
+      extend_failed_.erase(g);
+      pending_reqs_.erase(pending_reqs_.lower_bound({g, 0}), pending_reqs_.lower_bound({g + 1, 0}));
+    }
+  }
+  std::vector<uint32_t> list_groups(uint32_t which, uint32_t g0 = 0, uint32_t n = UINT32_MAX) {
+    if (n == UINT32_MAX) n = (uint32_t)stores_.size() - g0;
+    std::vector<uint32_t> out(n);
+    size_t total = 0;
+    check(jg_engine_list_groups(e_, which, g0, n, out.data(), out.size(), &total));
+    out.resize(std::min<size_t>(total, n));
+    return out;
+  }
+  std::vector<uint32_t> vacant_groups(uint32_t g0 = 0, uint32_t n = UINT32_MAX) { return list_groups(JG_LIST_VACANT, g0, n); }
+  std::vector<uint32_t> hosted_groups(uint32_t g0 = 0, uint32_t n = UINT32_MAX) { return list_groups(JG_LIST_HOSTED, g0, n); }
   ~BatchedRaft() { jg_engine_destroy(e_); }
   BatchedRaft(const BatchedRaft&) = delete;
   BatchedRaft& operator=(const BatchedRaft&) = delete;
