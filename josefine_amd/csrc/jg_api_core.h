@@ -268,14 +268,18 @@ struct jg_engine {
   }* drain_thread = nullptr;
   hipStream_t copy_stream = nullptr;
   hipEvent_t ev_steps = nullptr, ev_scan = nullptr, ev_done = nullptr;
-  // jg_engine_read_chains: the two staging buffers of its row pieces and the stream that copies them out (kept from the
-  // first read on: a read of a large image is not charged an allocation of its staging every time)
-  struct ReadStage {
+  // the staging of the control-plane calls (jg_api_manage.h: load, read, move, hosting): one growable device buffer - the
+  // hosting calls' scratch, or the two piece buffers of a staged download (a read's rows, an export's records) - with the
+  // stream that copies pieces out, an event per buffer for its kernel and one for its copy.  Kept from the first use on (a
+  // read of a large image is not charged an allocation every time); those calls are synchronous, one has it at a time
+  struct Staging {
     char* buf = nullptr;
     size_t bytes = 0;
     hipStream_t cs = nullptr;
     hipEvent_t ev_k[2]{}, ev_c[2]{};
-  } read_stage;
+    int reserve(size_t want);
+    int streams();
+  } staging;
   // two sets of the device-side fault / exceptional-row queues: kernels append to [cur_set] while
   // the other one is being copied out
   JgFaultRec* fq[2] = {nullptr, nullptr};

@@ -171,10 +171,11 @@ void jg_engine_destroy(jg_engine* e) {
   if (e->ev_scan) (void)hipEventDestroy(e->ev_scan);
   if (e->ev_done) (void)hipEventDestroy(e->ev_done);
   if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
-  if (e->read_stage.cs) (void)hipStreamSynchronize(e->read_stage.cs), (void)hipStreamDestroy(e->read_stage.cs);
-  for (hipEvent_t ev : {e->read_stage.ev_k[0], e->read_stage.ev_k[1], e->read_stage.ev_c[0], e->read_stage.ev_c[1]})
+  // the control-plane staging (jg_api_manage.h)
+  if (e->staging.cs) (void)hipStreamSynchronize(e->staging.cs), (void)hipStreamDestroy(e->staging.cs);
+  for (hipEvent_t ev : {e->staging.ev_k[0], e->staging.ev_k[1], e->staging.ev_c[0], e->staging.ev_c[1]})
     if (ev) (void)hipEventDestroy(ev);
-  if (e->read_stage.buf) (void)hipFree(e->read_stage.buf);
+  if (e->staging.buf) (void)hipFree(e->staging.buf);
   if (e->h_jobs) (void)hipHostFree(e->h_jobs);
   if (e->h_totals) (void)hipHostFree(e->h_totals);
   e->p_kind.destroy(), e->p_flag.destroy(), e->p_group.destroy(), e->p_from.destroy(), e->p_term.destroy();

@@ -1,25 +1,10 @@
 // jg_api_hosting.h - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups: vacant slots (jg_hosting.h).
-// Open and close follow jg_api_move.h's import: a check pass writes an error word, the host reads it, and only then does
-// the write pass run - on a multi-device handle only when every shard has passed.  The scratch (a host list and its own
-// slots, the error words; the list passes' workgroup counts and output) lives in the staging buffer the engine keeps for
-// jg_engine_read_chains (jg_engine::ReadStage): these calls are synchronous, nothing else uses it meanwhile.
-// Part of josefine_gpu.hip's one translation unit.
+// Open and close go through jg_api_manage.h's check_then_write: a check pass writes an error word, the host reads it, and
+// only then does the write pass run.  The scratch (a host list and its own slots, the error words; the list passes'
+// workgroup counts and output) is carved from the engine's staging.  Part of josefine_gpu.hip's one translation unit.
 #pragma once
 
 namespace {
-
-// e->read_stage.buf holds at least `bytes` (16-byte aligned pieces are carved from it by the callers)
-int stage_reserve(jg_engine* e, size_t bytes) {
-  jg_engine::ReadStage& st = e->read_stage;
-  if (st.bytes >= bytes) return JG_OK;
-  if (st.buf) HIPCHK(hipFree(st.buf));
-  st.buf = nullptr, st.bytes = 0;
-  HIPCHK(hipMalloc((void**)&st.buf, bytes));
-  st.bytes = bytes;
-  return JG_OK;
-}
-
-inline size_t align16(size_t b) { return (b + 15) & ~size_t(15); }
 
 // one single-device engine's part of an open or a close
 struct JgGroupsJob {
@@ -45,12 +30,10 @@ int groups_check(JgGroupsJob& j) {
     if (rc) return rc;
   }
   const bool host_list = j.list && !j.device, host_self = j.self && !j.device;
-  const size_t o_err = 0, o_list = 16, o_self = o_list + (host_list ? align16((size_t)j.n * 4) : 0);
-  {
-    const int rc = stage_reserve(e, o_self + (host_self ? align16(j.n) : 0));
-    if (rc) return rc;
-  }
-  char* B = e->read_stage.buf;
+  Carve c;
+  const size_t o_err = c.sect(8), o_list = host_list ? c.sect((size_t)j.n * 4) : 0, o_self = host_self ? c.sect(j.n) : 0;
+  char* B = nullptr;
+  if (const int rc = c.on_staging(e, B)) return rc;
   j.a = JgGroupsArgs{};
   j.a.g0 = j.g0, j.a.n = j.n, j.a.open = j.open ? 1u : 0u, j.a.seq = e->seq, j.a.now = j.now;
   j.a.err = (uint32_t*)(B + o_err);
@@ -86,13 +69,7 @@ int groups_write(JgGroupsJob& j) {
   else hipLaunchKernelGGL(k_groups_close, grid, dim3(JG_BLOCK), 0, e->stream, e->dev, j.a);
   HIPCHK(hipGetLastError());
   e->n_launch++;
-  // the engine's summaries of group state, as the import keeps them: flag words changed under the dense path's feet;
-  // one own slot for every group, or none
-  e->stepped = true;
-  e->maybe_irregular = true;
-  e->flag_check_pending = true;
-  e->irr_gen++;
-  if (j.open && e->uniform_self >= 0 && (j.err[1] & ~(1u << e->uniform_self))) e->uniform_self = -1;
+  groups_rewritten(e, j.open ? j.err[1] : 0);  // (err[1]: the mask of the own slots opened, from the check pass)
   HIPCHK(hipStreamSynchronize(e->stream));  // (the pageable list is done with)
   return JG_OK;
 }
@@ -105,56 +82,38 @@ int groups_call(jg_engine* e, bool open, uint64_t now_ms, const jg_group_set* s)
   if (!s->groups && (uint64_t)s->g0 + n > G) return fail(JG_EINVAL, std::string(what) + ": slot range out of bounds");
   if (!open && s->self_slots) return fail(JG_EINVAL, "jg_engine_close_groups: self_slots is for opening");
   if (device && e->router) return fail(JG_EINVAL, std::string(what) + ": device lists are per shard: a host list on a multi-device handle");
-  if (!e->router) {
-    const int rc0 = load_refuse(e);
-    if (rc0) return rc0;
-    JgGroupsJob j;
-    j.e = e, j.open = open, j.device = device, j.g0 = s->groups ? 0 : s->g0, j.n = n, j.list = s->groups;
-    j.self = s->self_slots, j.now = now_ms;
-    int rc = groups_check(j);
-    if (!rc) rc = groups_write(j);
-    return rc;
-  }
-  // a sharded handle: every shard's refusals, then every shard's part checked on its device, then the writes - one shard
-  // cannot refuse after another has written.  A host list is split by ownership with one binary search per shard, which
-  // needs it ascending and in range: checked here first (the devices check their parts again)
-  JgRouter& R = *e->router;
-  for (jg_engine* sh : R.sh) {
-    const int rc = load_refuse(sh);
-    if (rc) return rc;
-  }
+  if (const int rc = refuse_first(e, rewrite_refuse)) return rc;
+  // a sharded handle splits a host list by ownership with one binary search per shard, which needs it ascending and in
+  // range: checked here first (the devices check their parts again)
   const uint32_t* L = s->groups;
-  if (L) {
+  const bool split = L && e->router;
+  if (split) {
     for (uint32_t i = 0; i < n; i++) {
       if (L[i] >= G) return fail(JG_EINVAL, std::string(what) + ": a slot index is out of range (nothing was written)");
       if (i && L[i - 1] >= L[i]) return fail(JG_EINVAL, std::string(what) + ": the list is not strictly ascending (nothing was written)");
     }
   }
-  std::vector<JgGroupsJob> jobs(R.D());
-  for (size_t d = 0; d < R.D(); d++) {
-    JgGroupsJob& j = jobs[d];
-    j.e = R.sh[d], j.open = open, j.now = now_ms;
-    if (L) {
-      const uint32_t a = (uint32_t)(std::lower_bound(L, L + n, R.lo[d]) - L);
-      const uint32_t b = (uint32_t)(std::lower_bound(L, L + n, R.lo[d + 1]) - L);
-      if (a >= b) continue;
-      j.local.resize(b - a);
-      for (uint32_t i = a; i < b; i++) j.local[i - a] = L[i] - R.lo[d];
-      j.list = j.local.data(), j.n = b - a;
-      j.self = s->self_slots ? s->self_slots + a : nullptr;
-    } else {
-      const uint32_t a = std::max<uint32_t>(s->g0, R.lo[d]), b = std::min<uint32_t>(s->g0 + n, R.lo[d + 1]);
-      if (a >= b) continue;
-      j.g0 = a - R.lo[d], j.n = b - a;
-      j.self = s->self_slots ? s->self_slots + (a - s->g0) : nullptr;
-    }
-  }
-  int rc = R.run([&](size_t d) { return groups_check(jobs[d]); });
-  if (rc) return rc;
-  router_align_seq(e);
-  rc = R.run([&](size_t d) { return groups_write(jobs[d]); });
-  router_after_step(e);
-  return rc;
+  return check_then_write<JgGroupsJob>(
+      e,
+      [&](size_t d, JgGroupsJob& j) {
+        j.e = shard_at(e, d), j.open = open, j.device = device, j.now = now_ms;
+        uint32_t at = 0;  // the part's place in the caller's list and self_slots
+        if (split) {
+          const std::vector<uint32_t>& lo = e->router->lo;
+          at = (uint32_t)(std::lower_bound(L, L + n, lo[d]) - L);
+          const uint32_t b = (uint32_t)(std::lower_bound(L, L + n, lo[d + 1]) - L);
+          j.local.resize(b - at);
+          for (uint32_t i = at; i < b; i++) j.local[i - at] = L[i] - lo[d];
+          j.list = j.local.data(), j.n = b - at;
+        } else if (L) {
+          j.list = L, j.n = n;
+        } else {
+          const ShardPart p = shard_part(e, d, s->g0, n);
+          j.g0 = p.g0, j.n = p.n, at = p.at;
+        }
+        j.self = s->self_slots ? s->self_slots + at : nullptr;
+      },
+      groups_check, groups_write);
 }
 
 // one single-device engine's part of a list: shard-local slots [g0, g0 + n), the first `cap` matches (indices + add)
@@ -169,12 +128,10 @@ int list_shard(jg_engine* e, uint32_t which, uint32_t g0, uint32_t n, uint32_t a
   }
   const uint32_t tiles = (n + JG_LIST_TILE - 1) / JG_LIST_TILE;
   const size_t wcap = std::min<size_t>(cap, n);
-  const size_t o_total = 0, o_job = 16, o_bsum = 32, o_out = o_bsum + align16((size_t)tiles * 8);
-  {
-    const int rc = stage_reserve(e, o_out + align16(wcap * 4));
-    if (rc) return rc;
-  }
-  char* B = e->read_stage.buf;
+  Carve c;
+  const size_t o_total = c.sect(8), o_job = c.sect(sizeof(JgScanJob)), o_bsum = c.sect((size_t)tiles * 8), o_out = c.sect(wcap * 4);
+  char* B = nullptr;
+  if (const int rc = c.on_staging(e, B)) return rc;
   JgListArgs a{};
   a.g0 = g0, a.n = n, a.which = which, a.add = add;
   a.bsum = (uint64_t*)(B + o_bsum);
@@ -211,20 +168,20 @@ int jg_engine_list_groups(jg_engine* e, uint32_t which, uint32_t g0, uint32_t n,
   if (!e || !total || (cap && !out)) return fail(JG_EINVAL, "null argument");
   if (which != JG_LIST_VACANT && which != JG_LIST_HOSTED) return fail(JG_EINVAL, "jg_engine_list_groups: unknown `which`");
   if ((uint64_t)g0 + n > e->cfg.n_groups) return fail(JG_EINVAL, "jg_engine_list_groups: slot range out of bounds");
-  if (!e->router) return list_shard(e, which, g0, n, 0, out, cap, total);
+  if (!e->router) return list_shard(e, which, g0, n, 0, out, cap, total);  // (straight into the caller's array)
   // a sharded handle: the shards' answers concatenated in global order (each shard fills what is left of cap)
-  JgRouter& R = *e->router;
-  std::vector<size_t> tot(R.D(), 0);
-  std::vector<std::vector<uint32_t>> part(R.D());
-  int rc = R.run([&](size_t d) -> int {
-    const uint32_t a = std::max<uint32_t>(g0, R.lo[d]), b = std::min<uint32_t>(g0 + n, R.lo[d + 1]);
-    if (a >= b) return JG_OK;
-    part[d].resize(std::min<size_t>(cap, b - a));
-    return list_shard(R.sh[d], which, a - R.lo[d], b - a, R.lo[d], part[d].data(), part[d].size(), &tot[d]);
+  const size_t D = shard_count(e);
+  std::vector<size_t> tot(D, 0);
+  std::vector<std::vector<uint32_t>> part(D);
+  int rc = each_shard(e, [&](size_t d) -> int {
+    const ShardPart p = shard_part(e, d, g0, n);
+    if (!p.n) return JG_OK;
+    part[d].resize(std::min<size_t>(cap, p.n));
+    return list_shard(shard_at(e, d), which, p.g0, p.n, e->router->lo[d], part[d].data(), part[d].size(), &tot[d]);
   });
   if (rc) return rc;
   size_t all = 0;
-  for (size_t d = 0; d < R.D(); d++) {
+  for (size_t d = 0; d < D; d++) {
     const size_t k = std::min<size_t>(std::min<size_t>(tot[d], part[d].size()), cap > all ? cap - all : 0);
     if (k) std::memcpy(out + all, part[d].data(), k * 4);
     all += tot[d];

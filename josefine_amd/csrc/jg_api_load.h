@@ -1,16 +1,11 @@
 // jg_api_load.h - jg_engine_load_chains: an engine opened on the persisted chain trees of a process that restarts
 // (Raft::<Follower>::new + Chain::new on the sled directory, follower.rs:68-95, chain.rs:117-137).  The host checks the
 // image's shape, uploads it and launches the passes of jg_load.h; the ascending order of the ids is checked on the device,
-// ahead of every write.  Part of josefine_gpu.hip's one translation unit.
+// ahead of every write.  The refusals, the shards' parts and the step's bookkeeping are jg_api_manage.h's.  Part of
+// josefine_gpu.hip's one translation unit.
 #pragma once
 
 namespace {
-
-// what refuses a load before anything is touched (single-device engine)
-int load_refuse(const jg_engine* e) {
-  if (!e->p_kind.empty()) return fail(JG_EINVAL, "commands are queued: call jg_step first");
-  return kept_refuse(e);
-}
 
 // one single-device engine: groups [g0, g0 + n) of it, `off` rebased (off[0] == 0)
 int load_chains_shard(jg_engine* e, uint64_t now_ms, uint32_t g0, uint32_t n, const uint64_t* off, const uint64_t* id,
@@ -23,22 +18,13 @@ int load_chains_shard(jg_engine* e, uint64_t now_ms, uint32_t g0, uint32_t n, co
   }
   const uint64_t rows = off[n];
   const uint64_t tiles = std::max<uint64_t>((rows + JG_LOAD_TILE - 1) / JG_LOAD_TILE, 1);
-  // one scratch block: 8-byte sections first, then 4-byte, then 1-byte (16-byte aligned)
-  size_t at = 0;
-  auto sect = [&](size_t bytes) {
-    const size_t s = at;
-    at = (at + std::max<size_t>(bytes, 16) + 15) & ~size_t(15);
-    return s;
-  };
-  const size_t o_off = sect(((size_t)n + 1) * 8), o_id = sect(rows * 8), o_next = sect(rows * 8), o_commit = sect((size_t)n * 8),
-               o_bsum = sect(tiles * 8), o_total = sect(8), o_job = sect(sizeof(JgScanJob)), o_sx = sect(rows * 4),
-               o_err = sect(4), o_has = sect(n), o_st = sect(rows);
+  // one scratch block: 8-byte sections first, then 4-byte, then 1-byte
+  Carve c;
+  const size_t o_off = c.sect(((size_t)n + 1) * 8), o_id = c.sect(rows * 8), o_next = c.sect(rows * 8), o_commit = c.sect((size_t)n * 8),
+               o_bsum = c.sect(tiles * 8), o_total = c.sect(8), o_job = c.sect(sizeof(JgScanJob)), o_sx = c.sect(rows * 4),
+               o_err = c.sect(4), o_has = c.sect(n), o_st = c.sect(rows);
   char* B = nullptr;
-  HIPCHK(hipMalloc((void**)&B, at));
-  struct Free {
-    char* p;
-    ~Free() { (void)hipFree(p); }
-  } free_B{B};
+  if (const int rc = c.alloc(B)) return rc;
   JgLoadArgs a;
   a.n = n;
   a.g0 = g0;
@@ -71,14 +57,11 @@ int load_chains_shard(jg_engine* e, uint64_t now_ms, uint32_t g0, uint32_t n, co
     hipLaunchKernelGGL(k_load_place, dim3((uint32_t)((rows + JG_BLOCK - 1) / JG_BLOCK)), dim3(JG_BLOCK), 0, e->stream, e->dev, a);
     e->n_launch += 4;
   }
-  e->stepped = true;
+  groups_rewritten(e);  // (no own slot is written: a loaded group keeps its own)
   e->seq++;
   hipLaunchKernelGGL(k_load_groups, dim3((n + JG_BLOCK - 1) / JG_BLOCK), dim3(JG_BLOCK), 0, e->stream, e->dev, a, now_ms, e->seq);
   HIPCHK(hipGetLastError());
   e->n_launch++;
-  e->maybe_irregular = true;  // the flag words changed under the dense path's feet: re-read at the next synchronisation
-  e->flag_check_pending = true;
-  e->irr_gen++;
   uint32_t err = 0;
   HIPCHK(hipMemcpyAsync(&err, a.err, 4, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));  // (the pageable sources and the scratch block are done with)
@@ -102,36 +85,27 @@ int jg_engine_load_chains(jg_engine* e, uint64_t now_ms, const jg_chain_image* i
   const uint64_t rows = img->off[n];
   if (rows >= 0xffffffffull) return fail(JG_EINVAL, "jg_engine_load_chains: too many blocks in one call: split the range");
   if (rows && (!img->blk_id || !img->blk_next)) return fail(JG_EINVAL, "null argument");
-  if (!e->router) {
-    const int rc = load_refuse(e);
-    if (rc) return rc;
-    return load_chains_shard(e, now_ms, g0, n, img->off, img->blk_id, img->blk_next, img->commit, img->has_commit);
-  }
-  // a sharded handle: every shard is checked first, and the ascending order on the host as well - one device's refusal
-  // must not come after another device has loaded its part.  Then each shard loads its part on its own device.
-  JgRouter& r = *e->router;
-  for (jg_engine* s : r.sh) {
-    const int rc = load_refuse(s);
-    if (rc) return rc;
-  }
-  for (uint32_t i = 0; i < n; i++)
-    for (uint64_t k = img->off[i] + 1; k < img->off[i + 1]; k++)
-      if (img->blk_id[k] <= img->blk_id[k - 1])
-        return fail(JG_EINVAL, "jg_engine_load_chains: block ids are not strictly ascending within a group (nothing was loaded)");
-  router_align_seq(e);
-  std::vector<std::vector<uint64_t>> offs(r.D());
-  const int rc = r.run([&](size_t d) {
-    const uint32_t a = std::max<uint32_t>(g0, r.lo[d]), b = std::min<uint32_t>(g0 + n, r.lo[d + 1]);
-    if (a >= b) return (int)JG_OK;
-    std::vector<uint64_t>& o = offs[d];
-    o.resize(b - a + 1);
-    const uint64_t base = img->off[a - g0];
-    for (uint32_t i = a; i <= b; i++) o[i - a] = img->off[i - g0] - base;
-    return load_chains_shard(r.sh[d], now_ms, a - r.lo[d], b - a, o.data(), img->blk_id + base, img->blk_next + base,
-                             img->commit + (a - g0), img->has_commit + (a - g0));
+  if (const int rc = refuse_first(e, rewrite_refuse)) return rc;
+  // a sharded handle checks the ascending order on the host as well: one device's refusal must not come after another
+  // device has loaded its part.  Then each shard loads its part on its own device.
+  if (e->router)
+    for (uint32_t i = 0; i < n; i++)
+      for (uint64_t k = img->off[i] + 1; k < img->off[i + 1]; k++)
+        if (img->blk_id[k] <= img->blk_id[k - 1])
+          return fail(JG_EINVAL, "jg_engine_load_chains: block ids are not strictly ascending within a group (nothing was loaded)");
+  return write_shards(e, [&](size_t d) -> int {
+    const ShardPart p = shard_part(e, d, g0, n);
+    const uint64_t* off = img->off + p.at;
+    const uint64_t base = off[0];
+    std::vector<uint64_t> rebased;  // (a part that does not begin at the image's first row: its offsets from its own)
+    if (base) {
+      rebased.resize((size_t)p.n + 1);
+      for (uint32_t i = 0; i <= p.n; i++) rebased[i] = off[i] - base;
+      off = rebased.data();
+    }
+    return load_chains_shard(shard_at(e, d), now_ms, p.g0, p.n, off, img->blk_id + base, img->blk_next + base, img->commit + p.at,
+                             img->has_commit + p.at);
   });
-  router_after_step(e);
-  return rc;
 }
 
 }  // extern "C"

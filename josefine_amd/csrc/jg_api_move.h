@@ -1,8 +1,8 @@
 // jg_api_move.h - jg_engine_export_groups / jg_engine_import_groups: live groups handed between engines through a state
-// image (jg_move.h), without a restart.  A host-form export streams pieces of records through the two staging buffers of
-// jg_engine_read_chains (jg_engine::ReadStage): the kernel of piece k + 1 runs while piece k travels to the caller.  A
-// host-form import uploads the whole image into device scratch, validates every record (k_import_check) and only then
-// scatters it into the columns (k_import_groups).  Part of josefine_gpu.hip's one translation unit.
+// image (jg_move.h), without a restart.  A host-form export streams pieces of records through the engine's staging
+// (jg_api_manage.h's staged_pieces): the kernel of piece k + 1 runs while piece k travels to the caller.  A host-form
+// import uploads the whole image into device scratch, validates every record (k_import_check) and only then scatters it
+// into the columns (k_import_groups): jg_api_manage.h's check_then_write.  Part of josefine_gpu.hip's one translation unit.
 #pragma once
 
 #define JG_MOVE_PIECE (1u << 18)  // records per staging piece of a host-form export (a multiple of JG_MOVE_TILE)
@@ -35,13 +35,6 @@ int move_check_header(const jg_engine* e, const jg_group_image_header& h) {
   return JG_OK;
 }
 
-void launch_export(jg_engine* e, const JgMoveArgs& a) {
-  const dim3 grid((a.n + JG_MOVE_TILE - 1) / JG_MOVE_TILE);
-  if (jg_move_words(e->cfg.n_replicas) == 48) hipLaunchKernelGGL(k_export_groups<48>, grid, dim3(JG_BLOCK), 0, e->stream, e->dev, a);
-  else hipLaunchKernelGGL(k_export_groups<56>, grid, dim3(JG_BLOCK), 0, e->stream, e->dev, a);
-  e->n_launch++;
-}
-
 // one single-device engine's part of an export: groups [g0, g0 + n) into `dst` (host memory, or the device's own)
 int export_shard(jg_engine* e, uint32_t g0, uint32_t n, char* dst, bool device) {
   HIPCHK(hipSetDevice(e->device));
@@ -50,59 +43,32 @@ int export_shard(jg_engine* e, uint32_t g0, uint32_t n, char* dst, bool device) 
     if (rc) return rc;
   }
   if (!n) return JG_OK;
-  const size_t S = move_record_bytes(e);
-  JgMoveArgs a{};
   if (device) {
+    JgMoveArgs a{};
     a.g0 = g0, a.n = n, a.out = (uint4*)dst;
-    launch_export(e, a);
+    JG_LAUNCH_RECORDS(k_export_groups, e, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));
     return JG_OK;
   }
-  // pieces of JG_MOVE_PIECE records through two staging buffers: piece k is made on the engine's stream into buffer
-  // k & 1 and copied out on a stream of its own; piece k + 2 waits for that copy before it reuses the buffer
+  // pieces of JG_MOVE_PIECE records
+  const size_t S = move_record_bytes(e);
   const uint32_t P = (n + JG_MOVE_PIECE - 1) / JG_MOVE_PIECE, np = std::min<uint32_t>(n, JG_MOVE_PIECE);
-  jg_engine::ReadStage& st = e->read_stage;
-  if (st.bytes < 2 * np * S) {
-    if (st.buf) HIPCHK(hipFree(st.buf));
-    st.buf = nullptr, st.bytes = 0;
-    HIPCHK(hipMalloc((void**)&st.buf, 2 * np * S));
-    st.bytes = 2 * np * S;
-  }
-  if (!st.cs) {
-    HIPCHK(hipStreamCreateWithFlags(&st.cs, hipStreamNonBlocking));
-    for (uint32_t b = 0; b < 2; b++) {
-      HIPCHK(hipEventCreateWithFlags(&st.ev_k[b], hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&st.ev_c[b], hipEventDisableTiming));
-    }
-  }
-  char* buf[2] = {st.buf, st.buf + st.bytes / 2};
-  auto make = [&](uint32_t k) -> int {
-    const uint32_t b = k & 1u, r0 = k * JG_MOVE_PIECE;
-    if (k >= 2) HIPCHK(hipStreamWaitEvent(e->stream, st.ev_c[b], 0));
-    JgMoveArgs p{};
-    p.g0 = g0 + r0, p.n = std::min<uint32_t>(JG_MOVE_PIECE, n - r0), p.out = (uint4*)buf[b];
-    launch_export(e, p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(st.ev_k[b], e->stream));
-    return JG_OK;
-  };
-  auto copy = [&](uint32_t k) -> int {
-    const uint32_t b = k & 1u, r0 = k * JG_MOVE_PIECE, nr = std::min<uint32_t>(JG_MOVE_PIECE, n - r0);
-    HIPCHK(hipStreamWaitEvent(st.cs, st.ev_k[b], 0));
-    HIPCHK(hipMemcpyAsync(dst + (size_t)r0 * S, buf[b], (size_t)nr * S, hipMemcpyDeviceToHost, st.cs));
-    HIPCHK(hipEventRecord(st.ev_c[b], st.cs));
-    return JG_OK;
-  };
-  int rc = make(0);
-  // (a copy into pageable memory may return only when it is done: the next piece's kernel is queued before it)
-  for (uint32_t k = 1; k < P && !rc; k++)
-    if (!(rc = make(k))) rc = copy(k - 1);
-  if (!rc) rc = copy(P - 1);
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(st.cs));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return JG_OK;
+  return staged_pieces(
+      e, P, np * S,
+      [&](uint64_t k, char* buf) -> int {
+        const uint32_t r0 = (uint32_t)k * JG_MOVE_PIECE;
+        JgMoveArgs p{};
+        p.g0 = g0 + r0, p.n = std::min<uint32_t>(JG_MOVE_PIECE, n - r0), p.out = (uint4*)buf;
+        JG_LAUNCH_RECORDS(k_export_groups, e, p);
+        HIPCHK(hipGetLastError());
+        return JG_OK;
+      },
+      [&](uint64_t k, const char* buf) -> int {
+        const uint32_t r0 = (uint32_t)k * JG_MOVE_PIECE, nr = std::min<uint32_t>(JG_MOVE_PIECE, n - r0);
+        HIPCHK(hipMemcpyAsync(dst + (size_t)r0 * S, buf, (size_t)nr * S, hipMemcpyDeviceToHost, e->staging.cs));
+        return JG_OK;
+      });
 }
 
 // one single-device engine's part of an import: staged and validated first (check), written only when every part has
@@ -142,11 +108,8 @@ int import_check(JgImportJob& j) {
   if (!j.device) HIPCHK(hipMemcpyAsync(j.B, j.src, img, hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipMemsetAsync(j.d_err, 0, 8, e->stream));
   const JgMoveArgs a = import_args(j);
-  const dim3 grid((j.n + JG_MOVE_TILE - 1) / JG_MOVE_TILE);
-  if (jg_move_words(e->cfg.n_replicas) == 48) hipLaunchKernelGGL(k_import_check<48>, grid, dim3(JG_BLOCK), 0, e->stream, e->dev, a);
-  else hipLaunchKernelGGL(k_import_check<56>, grid, dim3(JG_BLOCK), 0, e->stream, e->dev, a);
+  JG_LAUNCH_RECORDS(k_import_check, e, a);
   HIPCHK(hipGetLastError());
-  e->n_launch++;
   HIPCHK(hipMemcpyAsync(j.err, j.d_err, 8, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   if (j.err[0] & 2u) return fail(JG_EDEVICE, "internal: jg_engine_import_groups met per-step deferral bits of a destination group between calls (nothing was imported)");
@@ -159,18 +122,9 @@ int import_write(JgImportJob& j) {
   if (!j.n) return JG_OK;
   HIPCHK(hipSetDevice(e->device));
   const JgMoveArgs a = import_args(j);
-  const dim3 grid((j.n + JG_MOVE_TILE - 1) / JG_MOVE_TILE);
-  if (jg_move_words(e->cfg.n_replicas) == 48) hipLaunchKernelGGL(k_import_groups<48>, grid, dim3(JG_BLOCK), 0, e->stream, e->dev, a);
-  else hipLaunchKernelGGL(k_import_groups<56>, grid, dim3(JG_BLOCK), 0, e->stream, e->dev, a);
+  JG_LAUNCH_RECORDS(k_import_groups, e, a);
   HIPCHK(hipGetLastError());
-  e->n_launch++;
-  // the engine's summaries of group state, as a step keeps them: the device's irregular_seen word (set by the kernel for
-  // a leader whose chain is not FAST) is re-read at the next synchronisation; one own slot for every group, or none
-  e->stepped = true;
-  e->maybe_irregular = true;
-  e->flag_check_pending = true;
-  e->irr_gen++;
-  if (e->uniform_self >= 0 && (j.err[1] & ~(1u << e->uniform_self))) e->uniform_self = -1;
+  groups_rewritten(e, j.err[1]);  // (err[1]: the mask of the own slots among the records, from the check pass)
   HIPCHK(hipStreamSynchronize(e->stream));  // (the pageable source and the scratch are done with)
   return JG_OK;
 }
@@ -190,20 +144,10 @@ int jg_engine_export_groups(jg_engine* e, jg_group_export* x) {
   const size_t S = move_record_bytes(e);
   if ((uint64_t)n * S > x->cap_bytes) return fail(JG_ECAPACITY, "jg_engine_export_groups: the records do not fit cap_bytes (the header is set)");
   if (n && !x->records) return fail(JG_EINVAL, "null argument");
-  if (!e->router) {
-    const int rc = kept_refuse(e);
-    if (rc) return rc;
-    return export_shard(e, g0, n, (char*)x->records, device);
-  }
-  JgRouter& R = *e->router;
-  for (jg_engine* s : R.sh) {
-    const int rc = kept_refuse(s);
-    if (rc) return rc;
-  }
-  return R.run([&](size_t d) {
-    const uint32_t a = std::max<uint32_t>(g0, R.lo[d]), b = std::min<uint32_t>(g0 + n, R.lo[d + 1]);
-    if (a >= b) return export_shard(R.sh[d], 0, 0, nullptr, false);
-    return export_shard(R.sh[d], a - R.lo[d], b - a, (char*)x->records + (size_t)(a - g0) * S, false);
+  if (const int rc = refuse_first(e, kept_refuse)) return rc;
+  return each_shard(e, [&](size_t d) -> int {
+    const ShardPart p = shard_part(e, d, g0, n);  // (a shard that owns none of the range still settles its steps)
+    return export_shard(shard_at(e, d), p.g0, p.n, (char*)x->records + (size_t)p.at * S, device);
   });
 }
 
@@ -219,38 +163,16 @@ int jg_engine_import_groups(jg_engine* e, const jg_group_import* x) {
   if (device && e->router) return fail(JG_EINVAL, "jg_engine_import_groups: device records are per shard: the host form on a multi-device handle");
   if (device && ((uintptr_t)x->records & 15u)) return fail(JG_EINVAL, "jg_engine_import_groups: device records must be 16-byte aligned");
   if (n && !x->records) return fail(JG_EINVAL, "null argument");
+  if (const int rc = refuse_first(e, rewrite_refuse)) return rc;
   const size_t S = move_record_bytes(e);
-  if (!e->router) {
-    const int rc0 = load_refuse(e);
-    if (rc0) return rc0;
-    JgImportJob j;
-    j.e = e, j.g0 = g0, j.n = n, j.src = (const char*)x->records, j.device = device, j.shift = (uint64_t)x->shift_ms;
-    int rc = import_check(j);
-    if (!rc) rc = import_write(j);
-    return rc;
-  }
-  // a sharded handle: every shard's refusals, then every shard's records validated on its device, then the writes - one
-  // shard cannot refuse after another has written
-  JgRouter& R = *e->router;
-  for (jg_engine* s : R.sh) {
-    const int rc = load_refuse(s);
-    if (rc) return rc;
-  }
-  std::vector<JgImportJob> jobs(R.D());
-  for (size_t d = 0; d < R.D(); d++) {
-    const uint32_t a = std::max<uint32_t>(g0, R.lo[d]), b = std::min<uint32_t>(g0 + n, R.lo[d + 1]);
-    jobs[d].e = R.sh[d];
-    jobs[d].shift = (uint64_t)x->shift_ms;
-    if (a >= b) continue;
-    jobs[d].g0 = a - R.lo[d], jobs[d].n = b - a;
-    jobs[d].src = (const char*)x->records + (size_t)(a - g0) * S;
-  }
-  int rc = R.run([&](size_t d) { return import_check(jobs[d]); });
-  if (rc) return rc;
-  router_align_seq(e);
-  rc = R.run([&](size_t d) { return import_write(jobs[d]); });
-  router_after_step(e);
-  return rc;
+  return check_then_write<JgImportJob>(
+      e,
+      [&](size_t d, JgImportJob& j) {
+        const ShardPart p = shard_part(e, d, g0, n);
+        j.e = shard_at(e, d), j.g0 = p.g0, j.n = p.n, j.device = device, j.shift = (uint64_t)x->shift_ms;
+        j.src = (const char*)x->records + (size_t)p.at * S;
+      },
+      import_check, import_write);
 }
 
 }  // extern "C"

@@ -38,6 +38,7 @@
 #include "jg_api_cluster.h"
 #include "jg_api_routed.h"
 #include "jg_api_misc.h"
+#include "jg_api_manage.h"
 #include "jg_api_load.h"
 #include "jg_api_read.h"
 #include "jg_api_move.h"
