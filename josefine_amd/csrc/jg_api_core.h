@@ -348,11 +348,11 @@ struct jg_engine {
     JgNodeRows rows{};
     size_t n = 0, nb = 0, fsm_rec_seq = 0;
     uint64_t now_ms = 0;
-    uint32_t flags = 0, col_mask = 0, seq_general = 0, seq_leader = 0, seq_follower = 0, seq_end = 0;
+    uint32_t flags = 0, col_mask = 0, seq_general = 0, seq_end = 0;
   };
   // What ONE node step leaves for the host.  A step owns a set until the next step begins - or, taken with JG_NODE_KEEP,
-  // until its outbox has been viewed: two such steps may be outstanding (the event loop's two ticks in flight), the newer
-  // one in NodeStep's own fields, the older one in NodeStep::spare (the sets change places when a step begins).
+  // until its outbox has been viewed: two such steps may be outstanding (the event loop's two ticks in flight), each in one
+  // of NodeStep::sets.
   struct NodeOut {
     jg_leader_beat* h_beat = nullptr;  // pinned mirrors of the outbox columns
     uint64_t *h_ae = nullptr, *h_answer = nullptr, *h_hbc = nullptr, *h_aec = nullptr;
@@ -384,9 +384,16 @@ struct jg_engine {
     size_t fsm_copied = 0;
     bool fsm_landed = false;           // l_fsm is to be handed to q_fsm by the next drain of that queue
     uint64_t irr_gen = 0;
-    uint32_t seq_lo = 0, seq_hi = 0;   // the engine's step numbers before and after the step
+    uint32_t seq_hi = 0;               // the engine's step number after the step
   };
-  struct NodeStep : NodeOut {
+  struct NodeStep {
+    // The two sets.  `newest` is the one the newest step took (a kept step takes the other one, a plain step the same one
+    // again); `kept_n` of them hold a kept step whose outbox has not been viewed: the newest, and with two the other too.
+    NodeOut sets[2];
+    uint32_t newest = 0, kept_n = 0;
+    NodeOut& cur() { return sets[newest]; }
+    // the set a view shows: the OLDEST outstanding step's - with none outstanding the newest's, which was viewed last
+    NodeOut& to_view() { return sets[kept_n == 2 ? newest ^ 1u : newest]; }
     bool ready = false;
     JgNodeCols cols{};
     uint64_t *h_in_answers = nullptr, *h_in_hbc = nullptr;  // pinned [R][G]: column inbound (jg_node_inbox_columns)
@@ -400,7 +407,7 @@ struct jg_engine {
     uint32_t* bk_mem = nullptr;
     uint32_t bk_words = 0, bk_buckets = 0, bk_tile_bits = 0;
     // the tiled row pass (jg_node.h, k_node_bin_* / k_node_tile): the chunks' counts per tile, the tiles' first rows, and the
-    // binned copies of a step's rows (grow-only; 38 bytes per row of room)
+    // binned copies of a step's rows (grow-only; 41 bytes per row of room)
     uint32_t *bin_cnt = nullptr, *bin_off = nullptr;
     char* bin_mem = nullptr;
     size_t bin_cap = 0;
@@ -408,19 +415,12 @@ struct jg_engine {
     uint32_t group_bits = 1;
     hipEvent_t ev_cols = nullptr;      // behind the uploads of the handed-out columns: the pinned buffers are free again
     bool cols_in_flight = false;
-    using Pending = NodePending;
-    // JG_NODE_KEEP: the other set (the OLDER outstanding step's while two are, a free one otherwise)
-    NodeOut spare;
-    // ... and the stream a kept step's outputs travel home on (the outbox columns, the fsm rows, the status block): the step's
+    // JG_NODE_KEEP: the stream a kept step's outputs travel home on (the outbox columns, the fsm rows, the status block): the step's
     // kernels do not queue up behind the previous step's copies - a tick's kernels are 0.3 ms, its trip home 1 ms
     hipStream_t down = nullptr;
-    uint32_t kept_n = 0;               // kept steps whose outbox has not been viewed (0 .. 2)
     bool in_step = false;              // node_step is running (its halves' own node_settle calls are not another caller's)
-    bool viewed_spare = false;         // the outbox viewed last is the spare set's
     size_t fsm_guess = 0;              // fsm rows of the kept step finished last: what the next one's own copy takes along
     bool fsm_guess_known = false;
-    NodeOut* fsm_visible = nullptr;    // the set whose l_fsm the next drain of the fsm queue hands over
-    NodeOut& own() { return *this; }
     // multi-device parent: the shards' columns concatenated
     std::vector<jg_leader_beat> cat_beat;
     std::vector<uint64_t> cat_ae, cat_answer, cat_hbc;

@@ -156,8 +156,9 @@ int drain_gather(jg_engine* e, jg_engine::DrainBatch& b, const std::vector<StepR
 }
 
 // host tail, once everything of the batch has landed: the rows count as queued, exceptional rows
-// are merged in by step sequence number, fault records are put in (step, group) order
-int drain_finish(jg_engine* e, jg_engine::DrainBatch& b, std::vector<StepRec>& recs, Arena& arena) {
+// are merged in by step sequence number, fault records are put in (step, group) order.  `arena`: the one the records
+// lived in, which starts over - or nullptr: it is the caller's to reset (a kept node step's, which holds more than records)
+int drain_finish(jg_engine* e, jg_engine::DrainBatch& b, std::vector<StepRec>& recs, Arena* arena) {
   const size_t nrec = recs.size();
   const uint64_t* totals = e->h_totals;
   PinnedQueue<jg_msg_row>& qm = b.to_landing ? e->l_msgs : e->q_msgs;
@@ -204,7 +205,7 @@ int drain_finish(jg_engine* e, jg_engine::DrainBatch& b, std::vector<StepRec>& r
   }
   if (nrec) {
     recs.clear();
-    arena.reset();
+    if (arena) arena->reset();
   }
   if (b.nf) {  // (sorted on the device)
     e->q_faults.insert(e->q_faults.end(), e->h_faults.p, e->h_faults.p + b.nf);
@@ -297,13 +298,13 @@ int inflight_finish(jg_engine* e) {
     }
     if (st[5]) e->maybe_irregular = true;
   }
-  return drain_finish(e, b, b.recs, e->arenas[b.arena]);
+  return drain_finish(e, b, b.recs, &e->arenas[b.arena]);
 }
 
 // `wait`: jg_drain_flush (block until the previous batch has landed); jg_drain_prefetch never
 // blocks: while a batch is still in transfer it starts nothing (the next call takes more steps)
 int drain_prefetch(jg_engine* e, bool wait) {
-  if (e->node.kept_n || e->node.keep) return fail(JG_EINVAL, "jg_drain_prefetch: the engine's node steps keep their outputs (JG_NODE_KEEP) - an engine overlaps its drains one way");
+  if (e->node.kept_n || e->node.cur().keep) return fail(JG_EINVAL, "jg_drain_prefetch: the engine's node steps keep their outputs (JG_NODE_KEEP) - an engine overlaps its drains one way");
   HIPCHK(hipSetDevice(e->device));
   {
     const int rc = node_settle(e);
@@ -367,7 +368,7 @@ int collect(jg_engine* e, int release_mask) {
   // JG_NODE_KEEP: what a viewed step left is in the queues already (its general-path rows, exceptional rows and faults) or
   // in its landing buffer (the fsm rows of its dense halves: handed over here, a pointer swap when the consumer has taken
   // everything before them); the device is not touched while kept steps are outstanding - their rows are not due yet
-  if (e->node.kept_n || e->node.fsm_landed || e->node.spare.fsm_landed) {
+  if (e->node.kept_n || e->node.sets[0].fsm_landed || e->node.sets[1].fsm_landed) {
     if (release_mask & 1) e->q_msgs.release_view();
     if (release_mask & 2) {
       e->q_fsm.release_view();
@@ -409,7 +410,7 @@ int collect(jg_engine* e, int release_mask) {
   if (rc) return rc;
   if (nrec || b.nf || b.nx) HIPCHK(hipStreamSynchronize(e->stream));
   const double t3 = now();
-  rc = drain_finish(e, b, e->recs, e->arenas[e->cur_arena]);
+  rc = drain_finish(e, b, e->recs, &e->arenas[e->cur_arena]);
   e->fault_floor[b.set] = b.seq_hi;  // (the set is empty again: whatever it collects next is later than this batch)
   if (trace && nrec)
     std::fprintf(stderr, "[jg drain] %zu steps: sync %.3f ms, scan %.3f ms, gather+copy %.3f ms, host tail %.3f ms (%zu msg rows, %u faults)\n",

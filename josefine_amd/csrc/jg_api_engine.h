@@ -180,8 +180,7 @@ void jg_engine_destroy(jg_engine* e) {
   if (e->h_totals) (void)hipHostFree(e->h_totals);
   e->p_kind.destroy(), e->p_flag.destroy(), e->p_group.destroy(), e->p_from.destroy(), e->p_term.destroy();
   e->p_id.destroy(), e->p_aux.destroy(), e->p_blk_id.destroy(), e->p_blk_next.destroy();
-  for (void* p : {(void*)e->node.h_beat, (void*)e->node.h_ae, (void*)e->node.h_answer, (void*)e->node.h_hbc, (void*)e->node.h_nsparse, (void*)e->node.h_aec,
-                  (void*)e->node.h_in_answers, (void*)e->node.h_in_hbc})
+  for (void* p : {(void*)e->node.h_in_answers, (void*)e->node.h_in_hbc})
     if (p) (void)hipHostFree(p);
   if (e->up.st) {
     (void)hipStreamSynchronize(e->up.st);
@@ -195,21 +194,16 @@ void jg_engine_destroy(jg_engine* e) {
   if (e->node.sp_key) (void)hipFree(e->node.sp_key);
   if (e->node.bin_mem) (void)hipFree(e->node.bin_mem);
   if (e->node.sp_idx) (void)hipFree(e->node.sp_idx);
-  if (e->node.ev_out) (void)hipEventDestroy(e->node.ev_out);
   if (e->node.down) {
     (void)hipStreamSynchronize(e->node.down);
     (void)hipStreamDestroy(e->node.down);
   }
-  for (jg_engine::NodeOut* o : {&e->node.spare, &e->node.own()}) {  // (JG_NODE_KEEP)
-    if (o == &e->node.spare) {
-      for (void* p : {(void*)o->h_beat, (void*)o->h_ae, (void*)o->h_answer, (void*)o->h_hbc, (void*)o->h_nsparse, (void*)o->h_aec})
-        if (p) (void)hipHostFree(p);
-      if (o->ev_out) (void)hipEventDestroy(o->ev_out);
-    }
-    if (o->h_status) (void)hipHostFree(o->h_status);
-    if (o->ev_early) (void)hipEventDestroy(o->ev_early);
-    if (o->ev_kernels) (void)hipEventDestroy(o->ev_kernels);
-    o->l_fsm.destroy();
+  for (jg_engine::NodeOut& o : e->node.sets) {  // (node_set_ensure, node_keep_ensure)
+    for (void* p : {(void*)o.h_beat, (void*)o.h_ae, (void*)o.h_answer, (void*)o.h_hbc, (void*)o.h_nsparse, (void*)o.h_aec, (void*)o.h_status})
+      if (p) (void)hipHostFree(p);
+    for (hipEvent_t ev : {o.ev_out, o.ev_early, o.ev_kernels})
+      if (ev) (void)hipEventDestroy(ev);
+    o.l_fsm.destroy();
   }
   if (e->node.ev_cols) (void)hipEventDestroy(e->node.ev_cols);
   e->q_msgs.destroy();

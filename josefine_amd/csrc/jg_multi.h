@@ -266,17 +266,18 @@ int router_step_node(jg_engine* p, uint64_t now_ms, uint32_t flags) {
   router_align_seq(p);
   const int rc = r.run([&](size_t d) { return node_step(r.sh[d], now_ms, flags); });
   router_after_step(p);
-  p->node.last_flags = flags;
+  p->node.cur().last_flags = flags;
   return rc;
 }
 // the shards' outbox columns, concatenated into the parent's group numbering
 int router_node_outbox(jg_engine* p, jg_node_outbox* out) {
   JgRouter& r = *p->router;
   jg_engine::NodeStep& nd = p->node;
-  if (!nd.last_flags) return fail(JG_EINVAL, "no jg_step_node yet");
+  const uint32_t last_flags = nd.cur().last_flags;
+  if (!last_flags) return fail(JG_EINVAL, "no jg_step_node yet");
   const size_t G = p->cfg.n_groups, R = p->cfg.n_replicas;
   *out = jg_node_outbox{};
-  const bool lead = (nd.last_flags & JG_NODE_LEADER_HALF) && (nd.last_flags & JG_NODE_TICK), fol = (nd.last_flags & JG_NODE_FOLLOWER_HALF) != 0;
+  const bool lead = (last_flags & JG_NODE_LEADER_HALF) && (last_flags & JG_NODE_TICK), fol = (last_flags & JG_NODE_FOLLOWER_HALF) != 0;
   if (lead) nd.cat_beat.resize(G), nd.cat_ae.resize(R * G);
   if (fol) nd.cat_answer.resize(G), nd.cat_hbc.resize(G);
   for (size_t d = 0; d < r.D(); d++) {

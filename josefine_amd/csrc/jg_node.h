@@ -329,7 +329,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_node_route(JgDev d, JgNodeCols c, 
 // the tile's rows to them (classification, a barrier, the scatter: LDS atomics), and writes the columns back in whole
 // lines.  What k_node_prefill wrote is the tile's initial value: that launch is gone too.  Results are the flat passes',
 // bit for bit (the binning carries every row's ARRIVAL INDEX: nothing depends on the order of a tile's rows) - the flat
-// kernels stay as the statement of it (JG_NODE_FLAT=1; tests/test_node_step.py::test_tiled_row_pass_equals_the_flat_one).
+// kernels stay as the statement of it (JG_CFG_FLAT_ROW_PASSES; tests/test_node_step.py::test_tiled_row_pass_equals_the_flat_one).
 #if JG_BLOCK == 256  // (the kernels: 256-thread workgroups; the one-lane and one-wave host builds of the tests run the flat passes)
 #define JGN_TILE_BITS 8u
 #define JGN_TILE (1u << JGN_TILE_BITS)  // partitions per tile: one per thread of the tile's workgroup

@@ -366,9 +366,12 @@ class BatchedRaft {
     check(jg_node_outbox_view(e_, &o));  // (the oldest open step's)
     ms_waited_for_outputs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
     last_outbox_ = o;
-    pending_blocks_.swap(step_blocks_.front());  // (nothing else is pending here: a plain step() is not taken between begin and finish)
+    // (what was noted since begin() - an AppendEntries submitted meanwhile - belongs to a later step: it waits for that one)
+    std::vector<std::pair<uint32_t, Block>> later = std::move(step_blocks_.front());
     step_blocks_.pop_front();
-    after_step();
+    later.swap(pending_blocks_);
+    after_step();  // (stores this step's blocks and leaves none pending)
+    pending_blocks_.insert(pending_blocks_.begin(), std::make_move_iterator(later.begin()), std::make_move_iterator(later.end()));
     if (columns_tx) columns_tx(o);
     else if (rpc_tx) expand_columns(o, answers_to);
   }
@@ -863,9 +866,9 @@ class BatchedEventLoop {
     }
     // (who THIS step's answers go to: noted per step, applied when the step is finished - with two ticks in flight the
     // step before is finished after this one has begun, and its answers go to the senders of ITS rows)
-    answers_of_step_.emplace_back();
-    for (size_t i = 0; i < in_.size(); i++)
-      if (in_.kind[i] == JG_CMD_HEARTBEAT || in_.kind[i] == JG_CMD_APPEND_ENTRIES) answers_of_step_.back().push_back({in_.group[i], in_.from[i]});
+    std::vector<std::pair<uint32_t, NodeId>> answers;
+    for (size_t i = 0; dense && i < in_.size(); i++)
+      if (in_.kind[i] == JG_CMD_HEARTBEAT || in_.kind[i] == JG_CMD_APPEND_ENTRIES) answers.push_back({in_.group[i], in_.from[i]});
     // payload-carrying rows (client proposals, blocks) go through submit() so that BatchedRaft's request /
     // block mirrors see them; everything else is one bulk jg_submit of the row queue
     for (auto& p : proposals_) raft_.note_proposal(p.group, p.id, std::move(p.data));
@@ -879,11 +882,11 @@ class BatchedEventLoop {
       if (!in_.empty()) raft_.submit_rows(in_.view());
       in_.clear();
       raft_.step_node_begin(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u), pipelined, two);
+      answers_of_step_.push_back(std::move(answers));  // (once the step has begun: one entry per open step, whatever begin() throws)
       last_at_ = at;
       if (pipelined) return;
       finish_oldest();
     } else {
-      answers_of_step_.pop_back();
       if (tick)
         for (uint32_t g = 0; g < G_; g++) in_.push(g, JG_CMD_TICK);
       if (!in_.empty()) raft_.submit_rows(in_.view());

@@ -568,6 +568,24 @@ static void pipelined_loop_is_the_plain_loop_later() {
 // holds a dead branch.  range(prev..commit) (follower.rs:204) walks the keys, so the dead block is
 // applied too, exactly as the reference's sled iterator would deliver it: ids 1 <- 2 <- 3 (dead) and
 // 2 <- 4 <- 5; commit 5 applies keys [0, 5) = 0, 1, 2, 3, 4 (genesis is skipped by the driver, fsm.rs:59-61).
+// A block noted while a node step is open (an AppendEntries submitted between step_node_begin and step_node_finish) is the
+// NEXT step's: finishing the open step neither drops it nor stores it early
+static void blocks_noted_while_a_node_step_is_open() {
+  BatchedRaft raft(1, {1, 2, 3});
+  raft.rpc_tx = [](const Message&) {};
+  CHECK(raft.handle(0).apply(Command::Heartbeat(1, 0, 2)).is_follower());
+  const uint32_t flags = JG_NODE_LEADER_HALF | JG_NODE_FOLLOWER_HALF | JG_NODE_TICK;
+  raft.submit(0, Command::AppendEntries(1, 2, {Block{1, 0, {7}}}));
+  raft.step_node_begin(10, flags, true);
+  raft.submit(0, Command::AppendEntries(1, 2, {Block{2, 1, {8}}}));
+  raft.step_node_finish();
+  CHECK(raft.store(0).has(1) && !raft.store(0).has(2) && raft.handle(0).head() == 1);
+  raft.step_node_begin(20, flags, true);
+  raft.step_node_finish();
+  CHECK(raft.store(0).has(2) && raft.store(0).at(2).data == std::vector<uint8_t>{8});
+  CHECK(raft.handle(0).head() == 2 && raft.handle(0).fault() == 0);
+}
+
 static void fsm_apply_walks_keys_not_parents() {
   BatchedRaft raft(1, {1, 2, 3});
   std::vector<uint8_t> seen;
@@ -632,6 +650,7 @@ int main() {
     chain_store_restart();
     event_loops_over_the_wire();
     pipelined_loop_is_the_plain_loop_later();
+    blocks_noted_while_a_node_step_is_open();
     fsm_apply_walks_keys_not_parents();
     fsm_fanout_throughput();
 #ifndef JG_TEST_AGAINST_ORACLE

@@ -43,6 +43,14 @@ def test_the_node_steps_bus_formats_on_the_emulated_device():
     assert "3 passed" in out, out[-500:]
 
 
+def test_kept_node_steps_on_the_emulated_device():
+    """JG_NODE_KEEP through the engine's host code - which set a step claims, which one a view shows, what a refused step
+    leaves behind: the rules at the boundary, a kept step refused with and without another one outstanding, and two ticks in
+    flight (the smallest case, and the compact bus formats' at G = 2000) against the oracle's synchronous steps"""
+    out = _run(["tests/test_node_step.py", "-m", "gpu", "-k", "keep_rules or refused_kept_step or (two_in_flight and (1-0-200 or 2000))"])
+    assert "5 passed" in out, out[-500:]
+
+
 def test_smoke_on_the_emulated_device():
     """__graft_entry__.smoke() as the driver calls it on the MI355X, here against the emulated build: elections through the
     general kernel, eight dense ticks of the ragged stream, six ticks through the Apply surface - every column, row and

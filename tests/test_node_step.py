@@ -737,6 +737,43 @@ def test_node_step_keep_rules():
     compare_snapshots(dev, ora, "the end")
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("outstanding", [True, False])
+def test_refused_kept_step_leaves_the_engine_as_it_was(outstanding):
+    """A kept step that is REFUSED (a column was handed out, the leader half does not run) claims nothing: kept step A - still
+    outstanding at the refusal, or viewed just before it - is what the next view shows and what the drains deliver, the
+    refusal consumed nothing (the column stays handed out), and kept step B with the leader half takes that column: B's
+    view, its drains and the state at the end equal the oracle's, which was given the same column."""
+    G, R = 300, 3
+    dev, ora, rng = mixed_pair(BatchedRaft, oracle_engine, G, R, seed=13, election_timeout_ms=(700, 1500))
+    fns = ("drain_messages", "drain_applies", "drain_faults")
+    col_slots = list(range(1, R))
+    cols = node_traffic(rng, ora, token0=0)
+    ora.submit_columns(**cols), dev.submit_columns(**cols)
+    want_a = (ora.step_node(100), {fn: getattr(ora, fn)() for fn in fns})
+    dev.step_node_begin(100, async_=True, keep=True)  # A
+    if not outstanding:
+        compare_outboxes(dev.node_outbox(), want_a[0], "A, viewed before the refusal")
+    rest, answer, hbc = split_columns(node_traffic(rng, ora, token0=1000), ora, col_slots)
+    for r in col_slots:
+        dev.node_inbox_columns(r, answer[r], hbc[r])
+    with pytest.raises(EngineError, match="a column was handed out"):
+        dev.step_node_begin(200, leader=False, async_=True, keep=True)
+    compare_outboxes(dev.node_outbox(), want_a[0], "A, after the refused step")
+    for fn, rows in want_a[1].items():
+        _same_rows(getattr(dev, fn)(), rows, f"A after the refused step: {fn}")
+    for r in col_slots:
+        ora.node_inbox_columns(r, answer[r], hbc[r])
+    ora.submit_columns(**rest), dev.submit_columns(**rest)
+    want_b = (ora.step_node(200), {fn: getattr(ora, fn)() for fn in fns})
+    dev.step_node_begin(200, async_=True, keep=True)  # B: the column handed out before the refusal goes with it
+    compare_outboxes(dev.node_outbox(), want_b[0], "B")
+    for fn, rows in want_b[1].items():
+        _same_rows(getattr(dev, fn)(), rows, f"B: {fn}")
+    assert len(want_a[1]["drain_applies"]) and len(want_b[1]["drain_applies"])
+    compare_snapshots(dev, ora, "the end")
+
+
 def _commit_in_place(dev, cols, extra_flags, lo=0, hi=None):
     """rows [lo, hi) of `cols` written straight into the engine's pinned columns (jg_submit_reserve / jg_submit_commit)"""
     import ctypes as C
