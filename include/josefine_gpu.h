@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 13u /* v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 14u /* v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -451,6 +451,66 @@ typedef struct jg_group_set {
 int jg_engine_open_groups(jg_engine* e, uint64_t now_ms, const jg_group_set* s);
 int jg_engine_close_groups(jg_engine* e, const jg_group_set* s);
 int jg_engine_list_groups(jg_engine* e, uint32_t which, uint32_t g0, uint32_t n, uint32_t* out, size_t cap, size_t* total);
+
+/* ---- the leadership feed and the census (ABI v14) ---------------------------------------------------
+ * Which partitions changed leader, who leads them now, and how many of each kind there are - answered on
+ * the device, so that a quiet engine costs a poll a few launches and 8 bytes over the bus instead of six
+ * jg_read_state columns and a diff on the host.
+ *
+ * The LEADERSHIP VIEW of a slot is a function of columns jg_read_state exposes (role, term, leader id,
+ * has-leader, fault, self slot) and nothing else:
+ *   - a leader:                 leader_id = node_ids[self_slot], state = KNOWN | SELF (the leader-id column,
+ *                               stale for a leader, is not consulted)
+ *   - a follower that knows a leader (follower.rs:20): leader_id = that id, state = KNOWN
+ *   - a candidate, a follower that knows none: leader_id = 0, no KNOWN
+ *   - a vacant slot (fault 255): state = VACANT, fault = 255, every other field 0 but self_slot
+ *   - a faulted slot (any other nonzero fault): as above from its frozen columns, FAULTED or-ed in
+ *
+ * jg_engine_watch_leaders compares the view of local slots g0 .. g0 + n - 1 with the engine's SHADOW - the
+ * view it last reported per slot, device memory allocated at the first call (16 bytes per slot; an engine
+ * that never watches pays nothing).  *total = the slots that differ in any field but group / self_slot;
+ * `out` (host memory) receives the first min(cap, total) of them ascending, as their current view; cap 0:
+ * the count only.  Exactly the slots whose rows were delivered become "seen": a small cap loses nothing
+ * (the rest is pending at the next call), and a delivered slot is reported again only when its view
+ * changes again.  JG_WATCH_PEEK delivers the same rows and advances nothing.  A watch starts as if every
+ * slot had last been reported vacant: a fresh hosted engine reports every slot once (followers at term 0),
+ * a JG_CFG_START_VACANT engine nothing until slots are opened.  Control-plane calls (open / close / load /
+ * import) are seen through the diff alone.  ONE feed per engine - the handle has one owner (server.rs:103-
+ * 165): two consumers of one engine would steal each other's changes.
+ *
+ * jg_engine_census counts what is over local slots g0 .. g0 + n - 1 in one reduction pass: integers,
+ * exact whatever order the reduction runs in.
+ *
+ * Both calls READ: they settle JG_NODE_ASYNC steps, refuse with JG_EINVAL while kept node steps are
+ * outstanding (as jg_engine_read_chains does; the kept steps stay viewable), and change nothing a step, a
+ * drain or jg_read_state can observe.  JG_EINVAL too for a null `total` / `out` (census), a null `out`
+ * with cap > 0, an unknown flag, a range out of bounds.  A multi-device parent handle answers in global
+ * slot order with `cap` over the whole answer (every shard is sized first, so a shard behind the point
+ * where cap ran out does not advance its shadow); its census is the shards' sum, max_term their maximum. */
+enum { JG_LEAD_KNOWN = 1u, JG_LEAD_SELF = 2u, JG_LEAD_VACANT = 4u, JG_LEAD_FAULTED = 8u };  /* jg_leader_row.state */
+enum { JG_WATCH_PEEK = 1u };          /* jg_engine_watch_leaders flags */
+typedef struct jg_leader_row {        /* 24 bytes */
+  uint32_t group;                     /* local slot (a sharded handle: index within the parent)     */
+  uint32_t leader_id;                 /* NodeId of the leader this replica knows, 0: none           */
+  uint64_t term;                      /* State.current_term                                         */
+  uint8_t role;                       /* JG_ROLE_*                                                  */
+  uint8_t state;                      /* JG_LEAD_*                                                  */
+  uint8_t fault;                      /* JG_FAULT_* (255: vacant)                                   */
+  uint8_t self_slot;
+  uint32_t reserved;                  /* 0                                                          */
+} jg_leader_row;
+typedef struct jg_census {
+  uint64_t hosted, vacant;
+  uint64_t faulted_reference, faulted_engine;  /* fault 1..127, 128..254                            */
+  uint64_t followers, candidates, leaders;     /* hosted and not faulted, by role                   */
+  uint64_t leaderless;                /* hosted, not faulted, no leader known                       */
+  uint64_t led_by[JG_MAX_REPLICAS];   /* ... known leader == node_ids[k]                            */
+  uint64_t led_by_other;              /* ... known leader outside the membership                    */
+  uint64_t max_term;                  /* over hosted slots, faulted included; 0 if none             */
+  uint64_t uncommitted;               /* sum of head - commit over the healthy leaders, mod 2^64    */
+} jg_census;
+int jg_engine_watch_leaders(jg_engine* e, uint32_t flags, uint32_t g0, uint32_t n, jg_leader_row* out, size_t cap, size_t* total);
+int jg_engine_census(jg_engine* e, uint32_t g0, uint32_t n, jg_census* out);
 
 /* ---- shards of a multi-device engine ------------------------------------------------------------
  * Everything that takes HOST memory works on the parent handle exactly as on a single-device

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -202,6 +202,24 @@ class GroupSet(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+LEAD_KNOWN, LEAD_SELF, LEAD_VACANT, LEAD_FAULTED = 1, 2, 4, 8  # jg_leader_row.state
+WATCH_PEEK = 1
+
+
+class LeaderRow(C.Structure):
+    """jg_leader_row."""
+    _fields_ = [("group", C.c_uint32), ("leader_id", C.c_uint32), ("term", C.c_uint64), ("role", C.c_uint8), ("state", C.c_uint8),
+                ("fault", C.c_uint8), ("self_slot", C.c_uint8), ("reserved", C.c_uint32)]
+
+
+class Census(C.Structure):
+    """jg_census."""
+    _fields_ = [("hosted", C.c_uint64), ("vacant", C.c_uint64), ("faulted_reference", C.c_uint64), ("faulted_engine", C.c_uint64),
+                ("followers", C.c_uint64), ("candidates", C.c_uint64), ("leaders", C.c_uint64), ("leaderless", C.c_uint64),
+                ("led_by", C.c_uint64 * MAX_REPLICAS), ("led_by_other", C.c_uint64), ("max_term", C.c_uint64),
+                ("uncommitted", C.c_uint64)]
+
+
 # mailbox words (josefine_gpu.h: JG_ANSWER / JG_AE)
 MAILBOX_NONE = (1 << 56) - 1
 
@@ -241,6 +259,8 @@ MSG_DTYPE = [("group", "<u4"), ("kind", "u1"), ("to_kind", "u1"), ("flag", "u1")
 FSM_DTYPE = [("group", "<u4"), ("kind", "u1"), ("pad", "u1", (3,)), ("a", "<u8"), ("b", "<u8")]
 FAULT_DTYPE = [("group", "<u4"), ("code", "<u4")]
 COMPACT_DTYPE = [("group", "<u4"), ("pad", "<u4"), ("id", "<u8")]
+LEADER_ROW_DTYPE = [("group", "<u4"), ("leader_id", "<u4"), ("term", "<u8"), ("role", "u1"), ("state", "u1"), ("fault", "u1"),
+                    ("self_slot", "u1"), ("reserved", "<u4")]
 
 _P = C.c_void_p
 
@@ -315,6 +335,8 @@ class Api:
         "engine_open_groups": (C.c_int, [_P, C.c_uint64, C.POINTER(GroupSet)]),
         "engine_close_groups": (C.c_int, [_P, C.POINTER(GroupSet)]),
         "engine_list_groups": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "engine_watch_leaders": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "engine_census": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(Census)]),
     }
     # only the oracle has these
     _ORACLE_PROTOS = {
@@ -358,4 +380,5 @@ HEADER_SYMBOLS = [
     "jg_step_node", "jg_node_outbox_view", "jg_submit_reserve", "jg_submit_commit", "jg_node_inbox_columns",
     "jg_engine_load_chains", "jg_engine_read_chains", "jg_engine_export_groups", "jg_engine_import_groups",
     "jg_engine_open_groups", "jg_engine_close_groups", "jg_engine_list_groups",
+    "jg_engine_watch_leaders", "jg_engine_census",
 ]

@@ -280,6 +280,9 @@ struct jg_engine {
     int reserve(size_t want);
     int streams();
   } staging;
+  // jg_engine_watch_leaders: the leadership view last reported per slot ([G] records of jg_watch.h, zero = "vacant");
+  // allocated at the first watch
+  uint4* watch_shadow = nullptr;
   // two sets of the device-side fault / exceptional-row queues: kernels append to [cur_set] while
   // the other one is being copied out
   JgFaultRec* fq[2] = {nullptr, nullptr};

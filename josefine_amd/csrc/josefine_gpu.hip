@@ -29,6 +29,7 @@
 #include "jg_read.h"
 #include "jg_move.h"
 #include "jg_hosting.h"
+#include "jg_watch.h"
 
 // The host side, by entry-point family (ONE translation unit: the pieces see each other's internals, in this order)
 #include "jg_api_core.h"
@@ -43,3 +44,4 @@
 #include "jg_api_read.h"
 #include "jg_api_move.h"
 #include "jg_api_hosting.h"
+#include "jg_api_watch.h"

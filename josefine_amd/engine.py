@@ -664,6 +664,33 @@ class BatchedRaft(_Hosting):
             self._check(self.api.read_state(self._h, fld, replica, out.ctypes.data, g0, n))
         return out
 
+    def watch_leaders(self, g0: int = 0, n: Optional[int] = None, limit: Optional[int] = None, peek: bool = False):
+        """jg_engine_watch_leaders: the slots of g0 .. g0 + n - 1 whose leadership view (role, term, known leader, fault,
+        vacancy) differs from what this feed last reported, ascending, as their current view: (rows, total) with rows a
+        structured array (capi.LEADER_ROW_DTYPE) of the first `limit` of them and total their number.  The delivered
+        slots become "seen"; `peek` delivers the same rows and advances nothing.  One feed per engine."""
+        n = self.G - int(g0) if n is None else int(n)
+        if not hasattr(self.api, "engine_watch_leaders"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_watch_leaders")
+        cap = n if limit is None else max(0, min(int(limit), n))
+        out = np.zeros(max(cap, 1), capi.LEADER_ROW_DTYPE)
+        total = C.c_size_t(0)
+        flags = capi.WATCH_PEEK if peek else 0
+        self._check(self.api.engine_watch_leaders(self._h, flags, int(g0), n, out.ctypes.data, cap, C.byref(total)))
+        return out[:min(cap, total.value)], int(total.value)
+
+    def census(self, g0: int = 0, n: Optional[int] = None) -> dict:
+        """jg_engine_census over the slots g0 .. g0 + n - 1: a dict of jg_census's fields (led_by: a list of R counts,
+        one per member of node_ids)."""
+        n = self.G - int(g0) if n is None else int(n)
+        if not hasattr(self.api, "engine_census"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_census")
+        c = capi.Census()
+        self._check(self.api.engine_census(self._h, int(g0), n, C.byref(c)))
+        out = {name: int(getattr(c, name)) for name, t in capi.Census._fields_ if name != "led_by"}
+        out["led_by"] = [int(x) for x in c.led_by[:self.R]]
+        return out
+
     def counters(self) -> dict:
         arr = (C.c_uint64 * 4)()
         self._check(self.api.get_counters(self._h, C.byref(arr)))

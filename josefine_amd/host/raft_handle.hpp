@@ -286,6 +286,28 @@ class BatchedRaft {
   }
   std::vector<uint32_t> vacant_groups(uint32_t g0 = 0, uint32_t n = UINT32_MAX) { return list_groups(JG_LIST_VACANT, g0, n); }
   std::vector<uint32_t> hosted_groups(uint32_t g0 = 0, uint32_t n = UINT32_MAX) { return list_groups(JG_LIST_HOSTED, g0, n); }
+  // The leadership feed and the census (jg_engine_watch_leaders / jg_engine_census, ABI v14; only callers need a library
+  // that has them): the slots of [g0, g0 + n) whose leadership view - role, term, known leader, fault, vacancy - differs
+  // from what this feed last reported, ascending, as their current view; at most `limit` rows, *total (if given) how many
+  // differ.  The delivered slots become "seen" unless `peek`.  What a broker serves Metadata's leader_id / leader_epoch
+  // from and keeps its LeaderAndIsr bookkeeping with, instead of one RaftHandle::role() round trip per partition.  ONE
+  // feed per engine: the event loop that owns the handle.
+  std::vector<jg_leader_row> watch_leaders(uint32_t g0 = 0, uint32_t n = UINT32_MAX, size_t limit = SIZE_MAX, bool peek = false,
+                                           size_t* total = nullptr) {
+    if (n == UINT32_MAX) n = (uint32_t)stores_.size() - g0;
+    std::vector<jg_leader_row> out(std::min<size_t>(limit, n));
+    size_t tot = 0;
+    check(jg_engine_watch_leaders(e_, peek ? (uint32_t)JG_WATCH_PEEK : 0u, g0, n, out.data(), out.size(), &tot));
+    out.resize(std::min<size_t>(tot, out.size()));
+    if (total) *total = tot;
+    return out;
+  }
+  jg_census census(uint32_t g0 = 0, uint32_t n = UINT32_MAX) {
+    if (n == UINT32_MAX) n = (uint32_t)stores_.size() - g0;
+    jg_census c{};
+    check(jg_engine_census(e_, g0, n, &c));
+    return c;
+  }
   ~BatchedRaft() { jg_engine_destroy(e_); }
   BatchedRaft(const BatchedRaft&) = delete;
   BatchedRaft& operator=(const BatchedRaft&) = delete;
