@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 14u /* v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 15u /* v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -511,6 +511,70 @@ typedef struct jg_census {
 } jg_census;
 int jg_engine_watch_leaders(jg_engine* e, uint32_t flags, uint32_t g0, uint32_t n, jg_leader_row* out, size_t cap, size_t* total);
 int jg_engine_census(jg_engine* e, uint32_t g0, uint32_t n, jg_census* out);
+
+/* ---- the replication feed and census (ABI v15) ------------------------------------------------------
+ * Which replicas of the partitions this engine leads are in sync, and which member is falling behind -
+ * the data of Partition.isr (src/broker/state/partition.rs:15), which the reference reports to every
+ * client (metadata.rs:93) and never maintains.  The facts live in the leader's ReplicationProgress
+ * (progress.rs:42-60,124); here they are decided on the device from 16 bytes per slot instead of
+ * 8R + 14 bytes of jg_read_state columns and a threshold and diff on the host.
+ *
+ * The REPLICATION VIEW is defined over columns jg_read_state exposes.  A slot LEADS for this feed if its
+ * role is leader and its fault is 0 (a vacant, a faulted slot, a follower, a candidate do not); for a slot
+ * that does not lead the view is all zero but group / self_slot.  For one that leads, with own slot s and
+ * every member slot r < R:
+ *   - lag_r = HEAD > MATCH_r ? HEAD - MATCH_r : 0 (saturating: a forged ack above the head counts as
+ *     caught up, and so does a progress head between head and the run's top on a restarted leader)
+ *   - the own slot is in sync by definition (MATCH_s is not consulted)
+ *   - membership is HYSTERETIC against what was last reported: was_r = the shadow says this slot led and
+ *     had bit r; in_r = was_r ? lag_r <= leave_lag : lag_r <= join_lag - a follower hovering at one
+ *     threshold would otherwise produce a row every tick
+ *   - isr: bit r = in_r; state = JG_ISR_LEADS | (popcount(isr) < R ? JG_ISR_UNDER : 0) |
+ *     (popcount(isr) < R / 2 + 1 ? JG_ISR_BELOW_QUORUM : 0)
+ *   - informational, NOT compared: replicate (the JG_FIELD_REPL_STATE mask), head, and worst_lag = the
+ *     largest lag_r over r != s (0 at R = 1)
+ *
+ * jg_engine_watch_replicas compares the view of local slots g0 .. g0 + n - 1 with the engine's SHADOW -
+ * the (isr, LEADS) it last reported per slot, device memory of its own allocated at the first call
+ * (4 bytes per slot; independent of the leadership feed's shadow).  *total = the slots whose (isr, LEADS)
+ * differs; `out` (host memory) receives the first min(cap, total) of them ascending, as their current
+ * view; cap 0: the count only.  Exactly the slots whose rows were delivered become "seen": a small cap
+ * loses nothing, JG_WATCH_PEEK delivers the same rows and advances nothing.  A zero-filled shadow means
+ * "not leading, empty set": a fresh engine reports nothing until something leads; a NEW LEADER reports
+ * {self}, and then each follower as its first acks arrive (join_lag applies to it; its members' progress
+ * starts at 0, so a leader whose head is within join_lag of 0 reports them at once).  Open, close, load,
+ * import and a loss of leadership are seen through the diff alone.  ONE feed per engine.
+ *
+ * jg_engine_replication_census is stateless: one threshold, no hysteresis, no shadow - a member of a led
+ * slot is in sync iff its lag <= lag_limit (the own slot always).  Integers, exact whatever order the
+ * reduction runs in.  out_of_sync[r] / max_lag[r] answer "which broker is slow".
+ *
+ * Both calls READ under the rules of the leadership feed: JG_NODE_ASYNC steps are settled first, JG_EINVAL
+ * while kept node steps are outstanding, for a null `e` / `total` / `out` (census) / policy, a null `out`
+ * with cap > 0, an unknown flag, a range out of bounds, join_lag > leave_lag.  A multi-device parent
+ * handle answers in global slot order with `cap` over the whole answer (every shard is sized first by a
+ * peek that delivers nothing; a shard behind the point where cap ran out keeps its shadow); its census
+ * sums the counts and the lag sums and takes the maximum of the maxima. */
+enum { JG_ISR_LEADS = 1u, JG_ISR_UNDER = 2u, JG_ISR_BELOW_QUORUM = 4u };  /* jg_isr_row.state */
+typedef struct jg_isr_policy { uint64_t leave_lag, join_lag; } jg_isr_policy;   /* join_lag <= leave_lag */
+typedef struct jg_isr_row {           /* 24 bytes: three 8-byte pieces */
+  uint32_t group;                     /* local slot (a sharded handle: index within the parent)     */
+  uint8_t isr;                        /* bit r: member r is in sync                                 */
+  uint8_t replicate;                  /* bit r: progress of r is Replicate (JG_FIELD_REPL_STATE)    */
+  uint8_t state;                      /* JG_ISR_*                                                   */
+  uint8_t self_slot;
+  uint64_t head;                      /* Chain.head of a slot that leads, else 0                    */
+  uint64_t worst_lag;                 /* max lag over the members but the own slot                  */
+} jg_isr_row;
+typedef struct jg_repl_census {
+  uint64_t leaders, fully_replicated, under_replicated, below_quorum;
+  uint64_t out_of_sync[JG_MAX_REPLICAS];   /* led slots where member r has lag > lag_limit (own slot never) */
+  uint64_t max_lag[JG_MAX_REPLICAS];       /* over the led slots, own slot 0                        */
+  uint64_t sum_lag[JG_MAX_REPLICAS];       /* mod 2^64                                              */
+  uint64_t max_uncommitted;                /* max of head - commit over the led slots               */
+} jg_repl_census;
+int jg_engine_watch_replicas(jg_engine* e, uint32_t flags, const jg_isr_policy* p, uint32_t g0, uint32_t n, jg_isr_row* out, size_t cap, size_t* total);
+int jg_engine_replication_census(jg_engine* e, uint64_t lag_limit, uint32_t g0, uint32_t n, jg_repl_census* out);
 
 /* ---- shards of a multi-device engine ------------------------------------------------------------
  * Everything that takes HOST memory works on the parent handle exactly as on a single-device

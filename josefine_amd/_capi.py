@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -220,6 +220,21 @@ class Census(C.Structure):
                 ("uncommitted", C.c_uint64)]
 
 
+ISR_LEADS, ISR_UNDER, ISR_BELOW_QUORUM = 1, 2, 4  # jg_isr_row.state
+
+
+class IsrPolicy(C.Structure):
+    """jg_isr_policy."""
+    _fields_ = [("leave_lag", C.c_uint64), ("join_lag", C.c_uint64)]
+
+
+class ReplCensus(C.Structure):
+    """jg_repl_census."""
+    _fields_ = [("leaders", C.c_uint64), ("fully_replicated", C.c_uint64), ("under_replicated", C.c_uint64),
+                ("below_quorum", C.c_uint64), ("out_of_sync", C.c_uint64 * MAX_REPLICAS), ("max_lag", C.c_uint64 * MAX_REPLICAS),
+                ("sum_lag", C.c_uint64 * MAX_REPLICAS), ("max_uncommitted", C.c_uint64)]
+
+
 # mailbox words (josefine_gpu.h: JG_ANSWER / JG_AE)
 MAILBOX_NONE = (1 << 56) - 1
 
@@ -261,6 +276,8 @@ FAULT_DTYPE = [("group", "<u4"), ("code", "<u4")]
 COMPACT_DTYPE = [("group", "<u4"), ("pad", "<u4"), ("id", "<u8")]
 LEADER_ROW_DTYPE = [("group", "<u4"), ("leader_id", "<u4"), ("term", "<u8"), ("role", "u1"), ("state", "u1"), ("fault", "u1"),
                     ("self_slot", "u1"), ("reserved", "<u4")]
+ISR_ROW_DTYPE = [("group", "<u4"), ("isr", "u1"), ("replicate", "u1"), ("state", "u1"), ("self_slot", "u1"), ("head", "<u8"),
+                 ("worst_lag", "<u8")]
 
 _P = C.c_void_p
 
@@ -337,6 +354,9 @@ class Api:
         "engine_list_groups": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "engine_watch_leaders": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "engine_census": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(Census)]),
+        "engine_watch_replicas": (C.c_int, [_P, C.c_uint32, C.POINTER(IsrPolicy), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                            C.POINTER(C.c_size_t)]),
+        "engine_replication_census": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(ReplCensus)]),
     }
     # only the oracle has these
     _ORACLE_PROTOS = {
@@ -381,4 +401,5 @@ HEADER_SYMBOLS = [
     "jg_engine_load_chains", "jg_engine_read_chains", "jg_engine_export_groups", "jg_engine_import_groups",
     "jg_engine_open_groups", "jg_engine_close_groups", "jg_engine_list_groups",
     "jg_engine_watch_leaders", "jg_engine_census",
+    "jg_engine_watch_replicas", "jg_engine_replication_census",
 ]

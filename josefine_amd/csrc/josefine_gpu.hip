@@ -30,6 +30,7 @@
 #include "jg_move.h"
 #include "jg_hosting.h"
 #include "jg_watch.h"
+#include "jg_isr.h"
 
 // The host side, by entry-point family (ONE translation unit: the pieces see each other's internals, in this order)
 #include "jg_api_core.h"
@@ -45,3 +46,4 @@
 #include "jg_api_move.h"
 #include "jg_api_hosting.h"
 #include "jg_api_watch.h"
+#include "jg_api_isr.h"

@@ -691,6 +691,38 @@ class BatchedRaft(_Hosting):
         out["led_by"] = [int(x) for x in c.led_by[:self.R]]
         return out
 
+    def watch_replicas(self, leave_lag: int, join_lag: Optional[int] = None, g0: int = 0, n: Optional[int] = None,
+                       limit: Optional[int] = None, peek: bool = False):
+        """jg_engine_watch_replicas: the slots of g0 .. g0 + n - 1 whose in-sync set (or whether the slot leads at all)
+        differs from what this feed last reported, ascending, as their current view: (rows, total) with rows a structured
+        array (capi.ISR_ROW_DTYPE) of the first `limit` of them and total their number.  A member the feed last reported
+        in sync stays while its lag is <= leave_lag, any other joins at lag <= join_lag (default: leave_lag).  The delivered
+        slots become "seen"; `peek` delivers the same rows and advances nothing.  One feed per engine."""
+        n = self.G - int(g0) if n is None else int(n)
+        if not hasattr(self.api, "engine_watch_replicas"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_watch_replicas")
+        cap = n if limit is None else max(0, min(int(limit), n))
+        out = np.zeros(max(cap, 1), capi.ISR_ROW_DTYPE)
+        total = C.c_size_t(0)
+        pol = capi.IsrPolicy(int(leave_lag), int(leave_lag if join_lag is None else join_lag))
+        flags = capi.WATCH_PEEK if peek else 0
+        self._check(self.api.engine_watch_replicas(self._h, flags, C.byref(pol), int(g0), n, out.ctypes.data, cap, C.byref(total)))
+        return out[:min(cap, total.value)], int(total.value)
+
+    def replication_census(self, lag_limit: int, g0: int = 0, n: Optional[int] = None) -> dict:
+        """jg_engine_replication_census over the slots g0 .. g0 + n - 1 with the one threshold lag_limit: a dict of
+        jg_repl_census's fields (out_of_sync / max_lag / sum_lag: lists of R values, one per member slot)."""
+        n = self.G - int(g0) if n is None else int(n)
+        if not hasattr(self.api, "engine_replication_census"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_replication_census")
+        c = capi.ReplCensus()
+        self._check(self.api.engine_replication_census(self._h, int(lag_limit), int(g0), n, C.byref(c)))
+        per_member = ("out_of_sync", "max_lag", "sum_lag")
+        out = {name: int(getattr(c, name)) for name, t in capi.ReplCensus._fields_ if name not in per_member}
+        for name in per_member:
+            out[name] = [int(x) for x in getattr(c, name)[:self.R]]
+        return out
+
     def counters(self) -> dict:
         arr = (C.c_uint64 * 4)()
         self._check(self.api.get_counters(self._h, C.byref(arr)))

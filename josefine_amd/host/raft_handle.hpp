@@ -308,6 +308,35 @@ class BatchedRaft {
     check(jg_engine_census(e_, g0, n, &c));
     return c;
   }
+  // The replication feed and its census (jg_engine_watch_replicas / jg_engine_replication_census, ABI v15; only callers
+  // need a library that has them): the slots of [g0, g0 + n) whose in-sync set - or whether the slot leads at all - differs
+  // from what this feed last reported, ascending, as their current view; at most `limit` rows, *total (if given) how many
+  // differ.  A member last reported in sync stays while its lag is <= policy.leave_lag, any other joins at lag <=
+  // policy.join_lag.  The delivered slots become "seen" unless `peek`.  What a broker keeps Partition.isr
+  // (partition.rs:15) and Metadata's isr_nodes (metadata.rs:93) with.  ONE feed per engine.
+  std::vector<jg_isr_row> watch_replicas(jg_isr_policy policy, uint32_t g0 = 0, uint32_t n = UINT32_MAX, size_t limit = SIZE_MAX,
+                                         bool peek = false, size_t* total = nullptr) {
+    if (n == UINT32_MAX) n = (uint32_t)stores_.size() - g0;
+    std::vector<jg_isr_row> out(std::min<size_t>(limit, n));
+    size_t tot = 0;
+    check(jg_engine_watch_replicas(e_, peek ? (uint32_t)JG_WATCH_PEEK : 0u, &policy, g0, n, out.data(), out.size(), &tot));
+    out.resize(std::min<size_t>(tot, out.size()));
+    if (total) *total = tot;
+    return out;
+  }
+  jg_repl_census replication_census(uint64_t lag_limit, uint32_t g0 = 0, uint32_t n = UINT32_MAX) {
+    if (n == UINT32_MAX) n = (uint32_t)stores_.size() - g0;
+    jg_repl_census c{};
+    check(jg_engine_replication_census(e_, lag_limit, g0, n, &c));
+    return c;
+  }
+  // an `isr` mask as the Vec<i32> of node ids Partition.isr holds, in member-slot order
+  std::vector<int32_t> isr_nodes(uint8_t isr) const {
+    std::vector<int32_t> out;
+    for (size_t r = 0; r < ids_.size() && r < JG_MAX_REPLICAS; r++)
+      if ((isr >> r) & 1u) out.push_back((int32_t)ids_[r]);
+    return out;
+  }
   ~BatchedRaft() { jg_engine_destroy(e_); }
   BatchedRaft(const BatchedRaft&) = delete;
   BatchedRaft& operator=(const BatchedRaft&) = delete;
