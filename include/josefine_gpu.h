@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 15u /* v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 16u /* v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -575,6 +575,48 @@ typedef struct jg_repl_census {
 } jg_repl_census;
 int jg_engine_watch_replicas(jg_engine* e, uint32_t flags, const jg_isr_policy* p, uint32_t g0, uint32_t n, jg_isr_row* out, size_t cap, size_t* total);
 int jg_engine_replication_census(jg_engine* e, uint64_t lag_limit, uint32_t g0, uint32_t n, jg_repl_census* out);
+
+/* ---- point queries: the state of a list of partitions (ABI v16) --------------------------------------
+ * "What is the state of exactly these partitions" - Metadata for some topics, the high watermark of the
+ * 500 partitions of a Fetch, the 2 000 a controller just moved - in one call: the batched form of
+ * RaftHandle's introspection (is_leader, get_term, ..., src/raft/mod.rs:437-468).  jg_read_state answers
+ * it per field over a range (one copy per column, decoded on the host) or per slot and field (two or more
+ * synchronous copies each); here one device pass gathers every field of every listed slot into one row.
+ *   - ANSWER ORDER: out[i] describes s->groups[i], in the order asked.  Unlike open and close the list need
+ *     NOT be ascending and MAY repeat an index: a request names partitions in its own order.
+ *   - groups == NULL is the range g0 .. g0 + n - 1: every jg_read_state field of a range in one pass.
+ *     self_slots is ignored.
+ *   - each field named after a JG_FIELD_* holds exactly the value jg_read_state returns for that field and
+ *     slot: a leader's commit decoded from the packed word, id_gen implicit while the chain is in FAST form,
+ *     leader_id 0 unless a follower that knows one, heartbeat_time 0 unless leader, the vote masks 0 unless
+ *     candidate, and so on.
+ *   - `state` and `known_leader` are the LEADERSHIP VIEW of jg_engine_watch_leaders (jg_leader_row.state /
+ *     .leader_id).  A vacant slot is JG_LEAD_VACANT with fault 255 and the canonical vacant columns.
+ *   - JG_LOOKUP_PROGRESS (needs match != NULL): match[i * R + r] = JG_FIELD_MATCH of replica r of entry i,
+ *     0 for a slot that is not a leader.  Without the flag `match` is not touched.
+ *   - it READS: it settles JG_NODE_ASYNC steps, refuses with JG_EINVAL while kept node steps are outstanding
+ *     (the kept steps stay viewable), does not see queued, unstepped commands, and changes nothing a step, a
+ *     drain, a feed or jg_read_state can observe.
+ *   - JG_EINVAL with `out` and `match` untouched for: a null `s`, a null `out` with n > 0, an unknown flag, an
+ *     index or a range out of bounds, JG_LOOKUP_PROGRESS without `match`, JG_GROUPS_DEVICE on a multi-device
+ *     parent handle.  A host list is checked on the host before anything is queued; a device list
+ *     (JG_GROUPS_DEVICE: the engine's own device memory) is checked on the device before any byte is copied
+ *     to the caller.  n = 0 is JG_OK.
+ *   - a multi-device parent handle takes a host list (or a range), lets every shard look up its entries and
+ *     answers in the order asked; `group` is the index within the parent. */
+enum { JG_LOOKUP_PROGRESS = 2u };     /* jg_group_set.flags for a lookup (bit 0 stays JG_GROUPS_DEVICE) */
+typedef struct jg_group_state {       /* 80 bytes: five 16-byte pieces */
+  uint32_t group;                     /* the index as asked (a sharded handle: index within the parent) */
+  uint32_t known_leader;              /* the leadership view's leader_id (jg_leader_row.leader_id)      */
+  uint64_t term, head, commit, id_gen;            /* JG_FIELD_TERM / HEAD / COMMIT / ID_GEN             */
+  uint64_t election_time, heartbeat_time;         /* JG_FIELD_ELECTION_TIME / HEARTBEAT_TIME            */
+  uint32_t voted_for, leader_id;                  /* JG_FIELD_VOTED_FOR / LEADER_ID                     */
+  uint32_t election_timeout, queued_reqs;         /* JG_FIELD_ELECTION_TIMEOUT / QUEUED_REQS            */
+  uint8_t role, state, fault, self_slot;          /* JG_FIELD_ROLE, JG_LEAD_* bits, FAULT, SELF_SLOT    */
+  uint8_t repl_state, vote_seen, vote_granted;    /* JG_FIELD_REPL_STATE / VOTE_SEEN / VOTE_GRANTED     */
+  uint8_t has;                                    /* bit 0 JG_FIELD_HAS_VOTED, bit 1 JG_FIELD_HAS_LEADER */
+} jg_group_state;
+int jg_engine_lookup_groups(jg_engine* e, const jg_group_set* s, jg_group_state* out, uint64_t* match /* [n][R] or NULL */);
 
 /* ---- shards of a multi-device engine ------------------------------------------------------------
  * Everything that takes HOST memory works on the parent handle exactly as on a single-device

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -193,6 +193,7 @@ class GroupImport(C.Structure):
 
 
 GROUPS_DEVICE = 1
+LOOKUP_PROGRESS = 2  # jg_group_set.flags of jg_engine_lookup_groups
 LIST_VACANT = 0
 LIST_HOSTED = 1
 
@@ -278,6 +279,11 @@ LEADER_ROW_DTYPE = [("group", "<u4"), ("leader_id", "<u4"), ("term", "<u8"), ("r
                     ("self_slot", "u1"), ("reserved", "<u4")]
 ISR_ROW_DTYPE = [("group", "<u4"), ("isr", "u1"), ("replicate", "u1"), ("state", "u1"), ("self_slot", "u1"), ("head", "<u8"),
                  ("worst_lag", "<u8")]
+# jg_group_state: a row of jg_engine_lookup_groups (80 bytes)
+GROUP_STATE_DTYPE = [("group", "<u4"), ("known_leader", "<u4"), ("term", "<u8"), ("head", "<u8"), ("commit", "<u8"), ("id_gen", "<u8"),
+                     ("election_time", "<u8"), ("heartbeat_time", "<u8"), ("voted_for", "<u4"), ("leader_id", "<u4"),
+                     ("election_timeout", "<u4"), ("queued_reqs", "<u4"), ("role", "u1"), ("state", "u1"), ("fault", "u1"),
+                     ("self_slot", "u1"), ("repl_state", "u1"), ("vote_seen", "u1"), ("vote_granted", "u1"), ("has", "u1")]
 
 _P = C.c_void_p
 
@@ -357,6 +363,7 @@ class Api:
         "engine_watch_replicas": (C.c_int, [_P, C.c_uint32, C.POINTER(IsrPolicy), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                             C.POINTER(C.c_size_t)]),
         "engine_replication_census": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(ReplCensus)]),
+        "engine_lookup_groups": (C.c_int, [_P, C.POINTER(GroupSet), C.c_void_p, C.c_void_p]),
     }
     # only the oracle has these
     _ORACLE_PROTOS = {
@@ -402,4 +409,5 @@ HEADER_SYMBOLS = [
     "jg_engine_open_groups", "jg_engine_close_groups", "jg_engine_list_groups",
     "jg_engine_watch_leaders", "jg_engine_census",
     "jg_engine_watch_replicas", "jg_engine_replication_census",
+    "jg_engine_lookup_groups",
 ]

@@ -31,6 +31,7 @@
 #include "jg_hosting.h"
 #include "jg_watch.h"
 #include "jg_isr.h"
+#include "jg_lookup.h"
 
 // The host side, by entry-point family (ONE translation unit: the pieces see each other's internals, in this order)
 #include "jg_api_core.h"
@@ -47,3 +48,4 @@
 #include "jg_api_hosting.h"
 #include "jg_api_watch.h"
 #include "jg_api_isr.h"
+#include "jg_api_lookup.h"

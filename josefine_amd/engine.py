@@ -723,6 +723,30 @@ class BatchedRaft(_Hosting):
             out[name] = [int(x) for x in getattr(c, name)[:self.R]]
         return out
 
+    def lookup(self, groups=None, g0: int = 0, n: Optional[int] = None, progress: bool = False):
+        """jg_engine_lookup_groups: the state of the listed slots, one row (capi.GROUP_STATE_DTYPE) per entry in the order
+        asked - every read(...) field of the slot plus its leadership view (`state`, `known_leader`).  `groups`: any integer
+        sequence or array, unsorted and with repeats; None: the range g0 .. g0 + n - 1.  With `progress`: (rows, match) with
+        match[i, r] the progress head of replica r of entry i (0 for a slot that is not a leader)."""
+        if not hasattr(self.api, "engine_lookup_groups"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_lookup_groups")
+        s = capi.GroupSet()
+        if groups is None:
+            s.g0, s.n = int(g0), self.G - int(g0) if n is None else int(n)
+            lst = None
+        else:
+            g = np.asarray(groups if isinstance(groups, np.ndarray) else list(groups)).reshape(-1)
+            if g.size and (g.dtype.kind not in "iu" or int(g.min()) < 0 or int(g.max()) >= (1 << 32)):
+                raise EngineError(capi.EINVAL, "slot index out of range")
+            lst = np.ascontiguousarray(g, dtype=np.uint32)
+            s.n, s.groups = lst.size, lst.ctypes.data
+        rows = np.zeros(s.n, capi.GROUP_STATE_DTYPE)
+        match = np.zeros((s.n, self.R), np.uint64) if progress else None
+        s.flags = capi.LOOKUP_PROGRESS if progress else 0
+        self._check(self.api.engine_lookup_groups(self._h, C.byref(s), rows.ctypes.data if s.n else None,
+                                                  match.ctypes.data if progress else None))
+        return (rows, match) if progress else rows
+
     def counters(self) -> dict:
         arr = (C.c_uint64 * 4)()
         self._check(self.api.get_counters(self._h, C.byref(arr)))

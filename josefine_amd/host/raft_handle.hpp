@@ -337,6 +337,26 @@ class BatchedRaft {
       if ((isr >> r) & 1u) out.push_back((int32_t)ids_[r]);
     return out;
   }
+  // Point queries (jg_engine_lookup_groups, ABI v16; only callers need a library that has it): the state of the n listed
+  // slots - any order, repeats allowed - one row per entry in the order asked: every RaftHandle getter's column of the slot
+  // and its leadership view (`state`: JG_LEAD_*, `known_leader`) from one device pass, instead of one jg_read_state round
+  // trip per partition and field.  With `progress`, match[i * R + r] is the progress head of member slot r of entry i (0
+  // for a slot that does not lead).  What a broker answers Metadata, ListOffsets or the high watermarks of a Fetch with.
+  struct GroupStates {
+    std::vector<jg_group_state> rows;
+    std::vector<uint64_t> match;  // [n][R] with progress, else empty
+  };
+  GroupStates lookup(const uint32_t* groups, size_t n, bool progress = false) {
+    jg_group_set s{};
+    s.n = (uint32_t)n, s.groups = groups;
+    return lookup_set(s, progress);
+  }
+  // ... of the range [g0, g0 + n)
+  GroupStates lookup(uint32_t g0, uint32_t n, bool progress = false) {
+    jg_group_set s{};
+    s.g0 = g0, s.n = n;
+    return lookup_set(s, progress);
+  }
   ~BatchedRaft() { jg_engine_destroy(e_); }
   BatchedRaft(const BatchedRaft&) = delete;
   BatchedRaft& operator=(const BatchedRaft&) = delete;
@@ -478,6 +498,15 @@ class BatchedRaft {
   friend class RaftHandle;
   void check(int rc) {
     if (rc != JG_OK) throw EngineError(rc, jg_last_error());
+  }
+  GroupStates lookup_set(jg_group_set& s, bool progress) {
+    GroupStates out;
+    out.rows.resize(s.n);
+    if (progress) out.match.resize((size_t)s.n * ids_.size()), s.flags |= JG_LOOKUP_PROGRESS;
+    // (an empty vector's data() may be null: JG_LOOKUP_PROGRESS wants a pointer even for no entries)
+    uint64_t none = 0;
+    check(jg_engine_lookup_groups(e_, &s, out.rows.data(), progress ? (out.match.empty() ? &none : out.match.data()) : nullptr));
+    return out;
   }
   void flush_rows() {
     if (kind_.empty()) return;
