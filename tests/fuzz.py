@@ -17,6 +17,14 @@ WEIGHTS = np.array([6, 1, 6, 10, 10, 16, 8, 4, 3, 1, 12, 2, 1], dtype=np.float64
 WEIGHTS /= WEIGHTS.sum()
 
 
+def _near(t, d):
+    """t + d for uint64 t and small signed d, not below 0: max(t + d, 0) without leaving 64 unsigned bits"""
+    below_zero = (d < 0) & (t < np.abs(d).astype(np.uint64))
+    with np.errstate(over="ignore"):
+        moved = t + d.astype(np.uint64)  # (a negative d wraps to 2^64 - |d|: the sum wraps back)
+    return np.where(below_zero, np.uint64(0), moved).astype(np.uint64)
+
+
 _TRACK = {}  # id(budget array) -> what random_batch remembers about the chains it has built (see below)
 
 
@@ -36,7 +44,7 @@ def random_batch(rng: np.random.Generator, ora, n: int, foreign_voters: bool = F
         if track is None or track["of"]() is not budget:  # (ids are reused once an array is gone)
             track = _TRACK[id(budget)] = {"of": weakref.ref(budget), "forks": {}, "hi": np.zeros(G, np.int64)}
     ids = np.array(ora.node_ids, dtype=np.uint32)
-    term_now = ora.read("term").astype(np.int64)
+    term_now = ora.read("term")  # (uint64: terms at and above 2^63 stay what they are - tests/wide_values.py)
     head_now = ora.read("head").astype(np.int64)
     commit_now = ora.read("commit").astype(np.int64)
     group = rng.integers(0, G, n).astype(np.uint32)
@@ -49,11 +57,11 @@ def random_batch(rng: np.random.Generator, ora, n: int, foreign_voters: bool = F
     # answers (election.rs:33-35); the engine remembers up to JG_FOREIGN_VOTERS distinct ones
     sid = np.uint32(4242) if not foreign_voters else (4242 + rng.integers(0, 6, n)).astype(np.uint32)
     from_ = np.where(stranger, sid, from_).astype(np.uint32)
-    term = np.maximum(term_now[group] + rng.integers(-1, 3, n), 0).astype(np.uint64)
+    term = _near(term_now[group], rng.integers(-1, 3, n))
     idv = np.maximum(head_now[group] + rng.integers(-2, 3, n), 0)
     use_commit = rng.random(n) < 0.3
     idv = np.where(use_commit, np.maximum(commit_now[group] + rng.integers(-1, 2, n), 0), idv).astype(np.uint64)
-    aux = np.maximum(term_now[group] + rng.integers(-1, 2, n), 0).astype(np.uint64)  # last_term
+    aux = _near(term_now[group], rng.integers(-1, 2, n))  # last_term
     flag = (rng.random(n) < 0.7).astype(np.uint8)
     blk_id, blk_next = [], []
     id_col = idv.copy()
@@ -114,7 +122,7 @@ def random_batch_aware(rng: np.random.Generator, ora, n: int, stats=None, p_wild
     ids = np.array(ora.node_ids, dtype=np.uint32)
     role = ora.read("role")
     fault = ora.read("fault")
-    term_now = ora.read("term").astype(np.int64)
+    term_now = ora.read("term")  # (uint64, read as Python ints below: wide terms stay what they are)
     head_now = ora.read("head").astype(np.int64)
     commit_now = ora.read("commit").astype(np.int64)
     id_gen = ora.read("id_gen").astype(np.int64)

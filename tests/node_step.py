@@ -267,3 +267,17 @@ def compare_outboxes(a, b, what=""):
         m = (a["answer"] != np.uint64(NO)) & ((a["answer"] & np.uint64(0xff)) != np.uint64(capi.HB_NONE))
         assert np.array_equal(a["hb_commit"][m], b["hb_commit"][m]), (what, "hb_commit")
     assert a["rows"] == b["rows"] and a["rows_general"] == b["rows_general"], (what, a["rows"], b["rows"], a["rows_general"], b["rows_general"])
+
+
+def pack_kind(cols, ids, R):
+    """JG_COL_PACKED_KIND: kind | sender slot << 4 | flag << 7 - and what the rows then SAY: a stranger (no slot: 7, R < 8)
+    reads NodeId 0, a kind without a sender reads 0 whatever the bits"""
+    kind, frm = cols["kind"], cols["from_"]
+    slot = np.full(len(kind), 7, np.uint8)
+    for r, i in enumerate(ids):
+        slot[frm == i] = r
+    carries = (kind >= capi.CMD_VOTE_REQUEST) & (kind <= capi.CMD_HEARTBEAT_RESPONSE)
+    table = np.array(list(ids) + [0] * (8 - R), np.uint32)
+    said = np.where(carries, table[slot], 0).astype(np.uint32)
+    packed = (kind | (slot << 4) | ((cols["flag"] != 0).astype(np.uint8) << 7)).astype(np.uint8)
+    return packed, said

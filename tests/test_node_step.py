@@ -18,6 +18,7 @@ import pytest
 from josefine_amd import BatchedRaft, EngineError, capi
 from node_step import (classify, columns_as_rows, compare_outboxes, elect_some, msgs_per_partition, node_traffic, plain_apply_equivalent,
                        rows_to_columns)
+from node_step import pack_kind as _pack_kind
 from oracle_lib import oracle_engine
 from parity import compare_drains, compare_snapshots
 
@@ -829,20 +830,6 @@ def test_node_step_early_upload_parity(R, flags, G):
         compare_snapshots(dev, ora, f"tick {t}")
         compare_drains(dev, ora, f"tick {t}")
     assert dev.counters()["decisions"] == ora.counters()["decisions"]
-
-
-def _pack_kind(cols, ids, R):
-    """JG_COL_PACKED_KIND: kind | sender slot << 4 | flag << 7 - and what the rows then SAY: a stranger (no slot: 7, R < 8)
-    reads NodeId 0, a kind without a sender reads 0 whatever the bits"""
-    kind, frm = cols["kind"], cols["from_"]
-    slot = np.full(len(kind), 7, np.uint8)
-    for r, i in enumerate(ids):
-        slot[frm == i] = r
-    carries = (kind >= capi.CMD_VOTE_REQUEST) & (kind <= capi.CMD_HEARTBEAT_RESPONSE)
-    table = np.array(list(ids) + [0] * (8 - R), np.uint32)
-    said = np.where(carries, table[slot], 0).astype(np.uint32)
-    packed = (kind | (slot << 4) | ((cols["flag"] != 0).astype(np.uint8) << 7)).astype(np.uint8)
-    return packed, said
 
 
 def _expand_common_ae(a, own, R):
