@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 16u /* v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 17u /* v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -617,6 +617,72 @@ typedef struct jg_group_state {       /* 80 bytes: five 16-byte pieces */
   uint8_t has;                                    /* bit 0 JG_FIELD_HAS_VOTED, bit 1 JG_FIELD_HAS_LEADER */
 } jg_group_state;
 int jg_engine_lookup_groups(jg_engine* e, const jg_group_set* s, jg_group_state* out, uint64_t* match /* [n][R] or NULL */);
+
+/* ---- the commit feed: what dense steps committed and appended (ABI v17) -------------------------------
+ * "Which partitions' high watermark advanced since I last looked, and from where to where?  Which got new
+ * blocks?" - the data of fsm::Driver (src/fsm.rs:20-93), of a Fetch long-poll, of a follower's store
+ * catching up.  The dense entry points (jg_step_dense_acks*, jg_step_dense_leader / _follower,
+ * jg_dense_cluster_rounds, the dense halves of jg_dense_cluster_round_routed) queue no FSM rows: their
+ * instructions are the per-group head / commit deltas.  Instead of two whole-range jg_read_state columns
+ * (16 bytes per slot over the bus) and a diff on the host per poll, the diff is made on the device.
+ *
+ * The COMMIT VIEW of a slot is (commit, head) exactly as jg_read_state returns JG_FIELD_COMMIT and
+ * JG_FIELD_HEAD: a leader's commit decoded from the packed word (the escape to the wide column and a base
+ * that is the run's top included); a vacant slot's view is (0, 0), a faulted slot's its frozen columns.
+ *
+ * The SHADOW is (commit_from, head_from) as last delivered: 16 bytes per slot, device memory of its own
+ * allocated zero-filled at the first call, independent of the other two feeds' shadows.  Zero means
+ * "genesis only": a fresh engine and a JG_CFG_START_VACANT engine report nothing until something is
+ * appended or committed.
+ *
+ * jg_engine_watch_commits compares the view of local slots g0 .. g0 + n - 1 with the shadow.  A slot
+ * DIFFERS iff commit != commit_from || head != head_from; with JG_WATCH_COMMITS_ONLY iff commit !=
+ * commit_from (a high-watermark consumer, which should not get a row for every append of a follower).
+ * *total = the slots that differ; `out` (host memory) receives the first min(cap, total) of them
+ * ascending; cap 0: the count only.  Exactly the delivered slots have BOTH shadow words advanced to the
+ * row's commit / head (under JG_WATCH_COMMITS_ONLY too): a small cap loses nothing, JG_WATCH_PEEK
+ * delivers the same rows and advances nothing.  ONE feed per engine, as for the other feeds.
+ *
+ * state: JG_CMT_COMMITTED commit > commit_from; JG_CMT_APPENDED head > head_from; JG_CMT_REWOUND either
+ * value went DOWN (a restart - head = commit -, a recreate, a close, a load, an import: the consumer
+ * resynchronises its store instead of applying a range); JG_CMT_LEADS role leader and fault 0;
+ * JG_CMT_VACANT fault 255; JG_CMT_FAULTED any other nonzero fault.  role / fault / self_slot are
+ * JG_FIELD_ROLE / FAULT / SELF_SLOT now; term is JG_FIELD_TERM now, informational and NOT compared.
+ *
+ * EXPANDING a row is the caller's convention, as the dense entry points document it: a leader - Apply for
+ * keys (commit_from, commit], Notify for ids (head_from, head]; a follower - Apply for keys
+ * [commit_from, commit) (JG_FSM_APPLY_LEADER / JG_FSM_APPLY_FOLLOWER {a = commit_from, b = commit}).
+ * Consecutive ranges concatenate exactly where the role did not change between two deliveries; a consumer
+ * that must know about a role change polls the leadership feed (jg_engine_watch_leaders) first.
+ *
+ * backlog, where not NULL, is filled from the counting pass: the state BEFORE this call's delivery, over
+ * EVERY slot of the range that differs (under the call's flags), delivered or not.  changed == *total.
+ * Integers, exact whatever order the reduction runs in.
+ *
+ * The call READS under the rules of jg_engine_watch_replicas: JG_NODE_ASYNC steps are settled first; it
+ * changes nothing a step, a drain, a read or the other feeds can observe; JG_EINVAL - with `out`, `total`,
+ * `backlog` and the shadow untouched - while kept node steps are outstanding, for a null `e` / `total`, a
+ * null `out` with cap > 0, an unknown flag, a range out of bounds.  A multi-device parent handle sizes
+ * every shard by a peek that delivers nothing (the backlog is the shards' sum from that pass), then each
+ * shard delivers into what is left of `cap`, in global slot order; a shard behind the point where cap ran
+ * out keeps its shadow.  Reading a node of a jg_dense_cluster between rounds is allowed. */
+enum { JG_CMT_COMMITTED = 1u, JG_CMT_APPENDED = 2u, JG_CMT_REWOUND = 4u,
+       JG_CMT_LEADS = 8u, JG_CMT_VACANT = 16u, JG_CMT_FAULTED = 32u };   /* jg_commit_row.state */
+enum { JG_WATCH_COMMITS_ONLY = 2u };   /* flags of jg_engine_watch_commits (bit 0 stays JG_WATCH_PEEK) */
+typedef struct jg_commit_row {         /* 48 bytes: three 16-byte pieces */
+  uint32_t group;                      /* local slot (a sharded handle: index within the parent) */
+  uint8_t role, state, fault, self_slot;
+  uint64_t term;                       /* JG_FIELD_TERM now - informational, NOT compared */
+  uint64_t commit_from, commit;        /* as last delivered / JG_FIELD_COMMIT now */
+  uint64_t head_from, head;            /* as last delivered / JG_FIELD_HEAD now   */
+} jg_commit_row;
+typedef struct jg_commit_backlog {     /* over ALL slots of the range that differ, delivered or not */
+  uint64_t changed, committed, appended, rewound;
+  uint64_t pending_commits;            /* sum of commit - commit_from where commit > commit_from, mod 2^64 */
+  uint64_t pending_appends;            /* sum of head - head_from where head > head_from, mod 2^64 */
+} jg_commit_backlog;
+int jg_engine_watch_commits(jg_engine* e, uint32_t flags, uint32_t g0, uint32_t n, jg_commit_row* out, size_t cap, size_t* total,
+                            jg_commit_backlog* backlog /* may be NULL */);
 
 /* ---- shards of a multi-device engine ------------------------------------------------------------
  * Everything that takes HOST memory works on the parent handle exactly as on a single-device

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -205,6 +205,7 @@ class GroupSet(C.Structure):
 
 LEAD_KNOWN, LEAD_SELF, LEAD_VACANT, LEAD_FAULTED = 1, 2, 4, 8  # jg_leader_row.state
 WATCH_PEEK = 1
+WATCH_COMMITS_ONLY = 2  # flags of jg_engine_watch_commits
 
 
 class LeaderRow(C.Structure):
@@ -227,6 +228,16 @@ ISR_LEADS, ISR_UNDER, ISR_BELOW_QUORUM = 1, 2, 4  # jg_isr_row.state
 class IsrPolicy(C.Structure):
     """jg_isr_policy."""
     _fields_ = [("leave_lag", C.c_uint64), ("join_lag", C.c_uint64)]
+
+
+# jg_commit_row.state
+CMT_COMMITTED, CMT_APPENDED, CMT_REWOUND, CMT_LEADS, CMT_VACANT, CMT_FAULTED = 1, 2, 4, 8, 16, 32
+
+
+class CommitBacklog(C.Structure):
+    """jg_commit_backlog."""
+    _fields_ = [("changed", C.c_uint64), ("committed", C.c_uint64), ("appended", C.c_uint64), ("rewound", C.c_uint64),
+                ("pending_commits", C.c_uint64), ("pending_appends", C.c_uint64)]
 
 
 class ReplCensus(C.Structure):
@@ -284,6 +295,9 @@ GROUP_STATE_DTYPE = [("group", "<u4"), ("known_leader", "<u4"), ("term", "<u8"),
                      ("election_time", "<u8"), ("heartbeat_time", "<u8"), ("voted_for", "<u4"), ("leader_id", "<u4"),
                      ("election_timeout", "<u4"), ("queued_reqs", "<u4"), ("role", "u1"), ("state", "u1"), ("fault", "u1"),
                      ("self_slot", "u1"), ("repl_state", "u1"), ("vote_seen", "u1"), ("vote_granted", "u1"), ("has", "u1")]
+# jg_commit_row: a row of jg_engine_watch_commits (48 bytes)
+COMMIT_ROW_DTYPE = [("group", "<u4"), ("role", "u1"), ("state", "u1"), ("fault", "u1"), ("self_slot", "u1"), ("term", "<u8"),
+                    ("commit_from", "<u8"), ("commit", "<u8"), ("head_from", "<u8"), ("head", "<u8")]
 
 _P = C.c_void_p
 
@@ -364,6 +378,8 @@ class Api:
                                             C.POINTER(C.c_size_t)]),
         "engine_replication_census": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(ReplCensus)]),
         "engine_lookup_groups": (C.c_int, [_P, C.POINTER(GroupSet), C.c_void_p, C.c_void_p]),
+        "engine_watch_commits": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                           C.POINTER(CommitBacklog)]),
     }
     # only the oracle has these
     _ORACLE_PROTOS = {
@@ -410,4 +426,5 @@ HEADER_SYMBOLS = [
     "jg_engine_watch_leaders", "jg_engine_census",
     "jg_engine_watch_replicas", "jg_engine_replication_census",
     "jg_engine_lookup_groups",
+    "jg_engine_watch_commits",
 ]

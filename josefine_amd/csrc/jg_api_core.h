@@ -286,6 +286,9 @@ struct jg_engine {
   // jg_engine_watch_replicas: the in-sync set last reported per slot ([G] words of jg_isr.h, zero = "not leading, empty");
   // allocated at the first watch
   uint32_t* isr_shadow = nullptr;
+  // jg_engine_watch_commits: the (commit, head) last delivered per slot ([G] records of jg_commits.h, zero = "genesis
+  // only"); allocated at the first watch
+  uint4* commit_shadow = nullptr;
   // two sets of the device-side fault / exceptional-row queues: kernels append to [cur_set] while
   // the other one is being copied out
   JgFaultRec* fq[2] = {nullptr, nullptr};

@@ -32,6 +32,7 @@
 #include "jg_watch.h"
 #include "jg_isr.h"
 #include "jg_lookup.h"
+#include "jg_commits.h"
 
 // The host side, by entry-point family (ONE translation unit: the pieces see each other's internals, in this order)
 #include "jg_api_core.h"
@@ -49,3 +50,4 @@
 #include "jg_api_watch.h"
 #include "jg_api_isr.h"
 #include "jg_api_lookup.h"
+#include "jg_api_commits.h"

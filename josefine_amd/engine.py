@@ -154,6 +154,20 @@ def expand_fsm_rows(rows: np.ndarray) -> np.ndarray:
     return out
 
 
+def commit_rows_as_fsm(rows: np.ndarray) -> np.ndarray:
+    """Rows of BatchedRaft.watch_commits (capi.COMMIT_ROW_DTYPE) as the FSM rows (capi.FSM_DTYPE) the dense entry points do
+    not queue: every row that is CMT_COMMITTED and not CMT_REWOUND becomes FSM_APPLY_LEADER (where CMT_LEADS: keys
+    (commit_from, commit]) or FSM_APPLY_FOLLOWER (keys [commit_from, commit)) {a = commit_from, b = commit}, in the rows'
+    order.  A rewound row has no range: the consumer resynchronises its store from the row's commit / head."""
+    rows = np.asarray(rows)
+    st = rows["state"]
+    r = rows[((st & capi.CMT_COMMITTED) != 0) & ((st & capi.CMT_REWOUND) == 0)]
+    out = np.zeros(len(r), dtype=capi.FSM_DTYPE)
+    out["group"], out["a"], out["b"] = r["group"], r["commit_from"], r["commit"]
+    out["kind"] = np.where(r["state"] & capi.CMT_LEADS, capi.FSM_APPLY_LEADER, capi.FSM_APPLY_FOLLOWER)
+    return out
+
+
 class _Hosting:
     """Vacant slots (ABI v13): open_groups / close_groups / vacant_groups / hosted_groups over an engine handle (a
     BatchedRaft, or one shard of a multi-device one)."""
@@ -746,6 +760,29 @@ class BatchedRaft(_Hosting):
         self._check(self.api.engine_lookup_groups(self._h, C.byref(s), rows.ctypes.data if s.n else None,
                                                   match.ctypes.data if progress else None))
         return (rows, match) if progress else rows
+
+    def watch_commits(self, g0: int = 0, n: Optional[int] = None, limit: Optional[int] = None, peek: bool = False,
+                      commits_only: bool = False, backlog: bool = False):
+        """jg_engine_watch_commits: the slots of g0 .. g0 + n - 1 whose (commit, head) - with `commits_only` whose commit -
+        differs from what this feed last delivered, ascending: (rows, total) with rows a structured array
+        (capi.COMMIT_ROW_DTYPE: commit_from / head_from as last delivered, commit / head now) of the first `limit` of them
+        and total their number; with `backlog` (rows, total, backlog) with the fields of jg_commit_backlog as a dict - every
+        differing slot of the range before this call's delivery.  The delivered slots become "seen"; `peek` delivers the
+        same rows and advances nothing.  One feed per engine."""
+        n = self.G - int(g0) if n is None else int(n)
+        if not hasattr(self.api, "engine_watch_commits"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_watch_commits")
+        cap = n if limit is None else max(0, min(int(limit), n))
+        out = np.zeros(max(cap, 1), capi.COMMIT_ROW_DTYPE)
+        total = C.c_size_t(0)
+        b = capi.CommitBacklog()
+        flags = (capi.WATCH_PEEK if peek else 0) | (capi.WATCH_COMMITS_ONLY if commits_only else 0)
+        self._check(self.api.engine_watch_commits(self._h, flags, int(g0), n, out.ctypes.data, cap, C.byref(total),
+                                                  C.byref(b) if backlog else None))
+        rows = out[:min(cap, total.value)]
+        if not backlog:
+            return rows, int(total.value)
+        return rows, int(total.value), {name: int(getattr(b, name)) for name, _ in capi.CommitBacklog._fields_}
 
     def counters(self) -> dict:
         arr = (C.c_uint64 * 4)()

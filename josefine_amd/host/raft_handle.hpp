@@ -357,6 +357,37 @@ class BatchedRaft {
     s.g0 = g0, s.n = n;
     return lookup_set(s, progress);
   }
+  // The commit feed (jg_engine_watch_commits, ABI v17; only callers need a library that has it): the slots of
+  // [g0, g0 + n) whose (commit, head) - with `commits_only` whose commit - differs from what this feed last delivered,
+  // ascending, each with the values last delivered and the values now; at most `limit` rows, *total (if given) how many
+  // differ, *backlog (if given) every differing slot of the range before this call's delivery.  The delivered slots
+  // become "seen" unless `peek`.  The fsm_tx of the dense entry points, which queue no FSM rows.  ONE feed per engine.
+  std::vector<jg_commit_row> watch_commits(uint32_t g0 = 0, uint32_t n = UINT32_MAX, size_t limit = SIZE_MAX, bool peek = false,
+                                           bool commits_only = false, size_t* total = nullptr, jg_commit_backlog* backlog = nullptr) {
+    if (n == UINT32_MAX) n = (uint32_t)stores_.size() - g0;
+    std::vector<jg_commit_row> out(std::min<size_t>(limit, n));
+    size_t tot = 0;
+    const uint32_t flags = (peek ? (uint32_t)JG_WATCH_PEEK : 0u) | (commits_only ? (uint32_t)JG_WATCH_COMMITS_ONLY : 0u);
+    check(jg_engine_watch_commits(e_, flags, g0, n, out.data(), out.size(), &tot, backlog));
+    out.resize(std::min<size_t>(tot, out.size()));
+    if (total) *total = tot;
+    return out;
+  }
+  // commit rows as the FSM rows a dense step does not queue: every row that is COMMITTED and not REWOUND becomes
+  // JG_FSM_APPLY_LEADER (where LEADS: keys (a, b]) or JG_FSM_APPLY_FOLLOWER (keys [a, b)) {a = commit_from, b = commit}; a
+  // rewound row has no range - the consumer resynchronises its store from the row's commit / head
+  static std::vector<jg_fsm_row> as_fsm_rows(const std::vector<jg_commit_row>& rows) {
+    std::vector<jg_fsm_row> out;
+    for (const jg_commit_row& r : rows) {
+      if (!(r.state & JG_CMT_COMMITTED) || (r.state & JG_CMT_REWOUND)) continue;
+      jg_fsm_row x{};
+      x.group = r.group;
+      x.kind = (r.state & JG_CMT_LEADS) ? (uint8_t)JG_FSM_APPLY_LEADER : (uint8_t)JG_FSM_APPLY_FOLLOWER;
+      x.a = r.commit_from, x.b = r.commit;
+      out.push_back(x);
+    }
+    return out;
+  }
   ~BatchedRaft() { jg_engine_destroy(e_); }
   BatchedRaft(const BatchedRaft&) = delete;
   BatchedRaft& operator=(const BatchedRaft&) = delete;
