@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 17u /* v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 18u /* v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -683,6 +683,58 @@ typedef struct jg_commit_backlog {     /* over ALL slots of the range that diffe
 } jg_commit_backlog;
 int jg_engine_watch_commits(jg_engine* e, uint32_t flags, uint32_t g0, uint32_t n, jg_commit_row* out, size_t cap, size_t* total,
                             jg_commit_backlog* backlog /* may be NULL */);
+
+/* ---- one poll per tick: the three feeds and the two censuses in one call (ABI v18) --------------------
+ * An event loop that consumes several feeds asks them of the same slots once per tick.  Asked separately
+ * every call is a round trip of its own: a settle, a count pass, a scan, a write pass, a synchronisation
+ * and a blocking row copy.  jg_engine_poll answers all the parts `want` names with ONE settle, ONE device
+ * pass over the slots (the flag word and the packed progress word read once: 88 bytes per slot instead
+ * of 104), one scan launch and ONE synchronisation.  It defines no value of its own:
+ *
+ * CONTRACT.  Let S be the separate calls that `want` names - jg_engine_watch_leaders (JG_POLL_LEADERS:
+ * leader_flags, leaders, leaders_cap, leaders_total), jg_engine_watch_replicas (JG_POLL_REPLICAS:
+ * replica_flags, policy, replicas, replicas_cap, replicas_total), jg_engine_watch_commits
+ * (JG_POLL_COMMITS: commit_flags, commits, commits_cap, commits_total, backlog - may be NULL),
+ * jg_engine_census (JG_POLL_CENSUS: census), jg_engine_replication_census (JG_POLL_REPL_CENSUS:
+ * census_lag_limit, repl_census) - each over local slots g0 .. g0 + n - 1.  The poll leaves exactly what
+ * S leaves when each is called on the same engine state: every output byte, every total, the backlog,
+ * and the three shadows.  The feeds do not observe each other, so no order among the parts is defined.
+ * A part NOT named is not computed: its shadow is neither allocated nor advanced and its fields of
+ * jg_poll are neither read nor written.  The poll and the separate calls share the shadows and may be
+ * mixed freely on one engine.
+ *
+ * ALL OR NOTHING.  Every argument of every wanted part is checked before anything is queued, by the
+ * separate calls' own rules: JG_EINVAL - no shadow advanced, no byte of any output or total written - for
+ * a null `e` / `p`, want == 0 or an unknown bit, an unknown flag in a wanted feed's flag word, join_lag >
+ * leave_lag, a null row array with a nonzero cap, a null census pointer of a wanted census, a range out
+ * of bounds, kept node steps outstanding.  n == 0 is JG_OK with totals 0 and zeroed censuses and backlog.
+ *
+ * It READS: JG_NODE_ASYNC steps are settled once; nothing a step, a drain, jg_read_state or a separate
+ * feed call can observe changes, the shadows as stated above excepted.  A multi-device parent handle
+ * sizes every shard by one fused peek that delivers nothing (the backlog and the censuses are the shards'
+ * sums or maxima from that pass), then each shard delivers into what is left of EACH feed's own cap, in
+ * global slot order; a shard behind the point where a feed's cap ran out keeps that feed's shadow. */
+enum { JG_POLL_LEADERS = 1u, JG_POLL_REPLICAS = 2u, JG_POLL_COMMITS = 4u,
+       JG_POLL_CENSUS = 8u, JG_POLL_REPL_CENSUS = 16u };   /* jg_poll.want */
+typedef struct jg_poll {
+  uint32_t want;                       /* JG_POLL_*; 0 is JG_EINVAL                              */
+  uint32_t g0, n;                      /* local slots g0 .. g0 + n - 1, for every part           */
+  uint32_t leader_flags;               /* JG_WATCH_PEEK                                          */
+  uint32_t replica_flags;              /* JG_WATCH_PEEK                                          */
+  uint32_t commit_flags;               /* JG_WATCH_PEEK | JG_WATCH_COMMITS_ONLY                  */
+  jg_isr_policy policy;                /* JG_POLL_REPLICAS                                       */
+  uint64_t census_lag_limit;           /* JG_POLL_REPL_CENSUS                                    */
+  jg_leader_row* leaders;              /* out: host memory, [leaders_cap]                        */
+  size_t leaders_cap, leaders_total;   /* in, out                                                */
+  jg_isr_row* replicas;
+  size_t replicas_cap, replicas_total;
+  jg_commit_row* commits;
+  size_t commits_cap, commits_total;
+  jg_commit_backlog* backlog;          /* out, may be NULL                                       */
+  jg_census* census;                   /* out: JG_POLL_CENSUS                                    */
+  jg_repl_census* repl_census;         /* out: JG_POLL_REPL_CENSUS                               */
+} jg_poll;
+int jg_engine_poll(jg_engine* e, jg_poll* p);
 
 /* ---- shards of a multi-device engine ------------------------------------------------------------
  * Everything that takes HOST memory works on the parent handle exactly as on a single-device

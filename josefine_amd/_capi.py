@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -247,6 +247,19 @@ class ReplCensus(C.Structure):
                 ("sum_lag", C.c_uint64 * MAX_REPLICAS), ("max_uncommitted", C.c_uint64)]
 
 
+POLL_LEADERS, POLL_REPLICAS, POLL_COMMITS, POLL_CENSUS, POLL_REPL_CENSUS = 1, 2, 4, 8, 16  # jg_poll.want
+
+
+class Poll(C.Structure):
+    """jg_poll."""
+    _fields_ = [("want", C.c_uint32), ("g0", C.c_uint32), ("n", C.c_uint32), ("leader_flags", C.c_uint32),
+                ("replica_flags", C.c_uint32), ("commit_flags", C.c_uint32), ("policy", IsrPolicy), ("census_lag_limit", C.c_uint64),
+                ("leaders", C.c_void_p), ("leaders_cap", C.c_size_t), ("leaders_total", C.c_size_t),
+                ("replicas", C.c_void_p), ("replicas_cap", C.c_size_t), ("replicas_total", C.c_size_t),
+                ("commits", C.c_void_p), ("commits_cap", C.c_size_t), ("commits_total", C.c_size_t),
+                ("backlog", C.POINTER(CommitBacklog)), ("census", C.POINTER(Census)), ("repl_census", C.POINTER(ReplCensus))]
+
+
 # mailbox words (josefine_gpu.h: JG_ANSWER / JG_AE)
 MAILBOX_NONE = (1 << 56) - 1
 
@@ -380,6 +393,7 @@ class Api:
         "engine_lookup_groups": (C.c_int, [_P, C.POINTER(GroupSet), C.c_void_p, C.c_void_p]),
         "engine_watch_commits": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                            C.POINTER(CommitBacklog)]),
+        "engine_poll": (C.c_int, [_P, C.POINTER(Poll)]),
     }
     # only the oracle has these
     _ORACLE_PROTOS = {
@@ -427,4 +441,5 @@ HEADER_SYMBOLS = [
     "jg_engine_watch_replicas", "jg_engine_replication_census",
     "jg_engine_lookup_groups",
     "jg_engine_watch_commits",
+    "jg_engine_poll",
 ]

@@ -1,0 +1,164 @@
+// jg_poll.h — gfx950 kernel of jg_engine_poll: the count passes of the three change feeds (jg_watch.h, jg_isr.h,
+// jg_commits.h) as ONE pass over the slots.
+//
+// A tick of an event loop that consumes several feeds asks "what changed leader, whose in-sync set changed, what was
+// committed or appended" of the same slots.  Asked separately the three count passes read 44 + 16 + 44 = 104 bytes per
+// slot; here the flag word and mlag are read once: 88 bytes where all three are wanted.  The views, the shadows and the
+// comparisons are the feeds' own - jg_lead_view, jg_isr_word, the commit decode of jg_commit_ballots - so the per-feed
+// cnt[tile] / bsum[tile] this pass writes are exactly what k_watch_write, k_isr_write and k_commit_write index, and the
+// commit backlog's partial records are what k_commit_backlog_sum adds up: those kernels run unchanged behind it.
+//
+//   k_poll_count<L, I, C>  the feeds wanted are launch-uniform template switches (two or three of them: a single feed has
+//                          its own count kernel); commits_only and backlog are launch-uniform words of the commit feed's
+//                          arguments, as in k_commit_count.  A workgroup strides over the tiles b, b + grid, ... and
+//                          walks a tile of four rows as passes of JG_POLL_FLIGHT rows: every distinct column of the
+//                          wanted feeds loaded once, all of a pass's loads in flight before the first use; per feed and
+//                          row one __ballot and one __popcll per wave, both 32-bit halves of every compared word
+//   k_scan_block_sums      (jg_sparse.h) one launch, one workgroup per wanted feed's bsum array
+//
+// Nothing here writes a column of the state machine or a shadow: the only stores are the scratch.
+#pragma once
+#include "jg_commits.h"
+#include "jg_isr.h"
+#include "jg_watch.h"
+
+static_assert(JG_WATCH_TILE == JG_ISR_TILE && JG_ISR_TILE == JG_CMT_TILE, "the three write passes index one tiling");
+#define JG_POLL_ROWS JG_CMT_ROWS
+#define JG_POLL_TILE JG_CMT_TILE
+// rows of a tile whose loads are in flight together: 22 dwords a row where all three feeds are wanted
+#define JG_POLL_FLIGHT 4u
+static_assert(JG_POLL_ROWS % JG_POLL_FLIGHT == 0, "a tile is whole passes");
+
+struct JgPollArgs {
+  uint32_t tiles;   // tiles of JG_POLL_TILE slots
+  uint32_t parts;   // workgroups of k_poll_count (<= JG_CMT_PARTS)
+  JgWatchArgs lw;   // the arguments of the wanted feeds' own write passes: g0 and n are the same in all of them
+  JgIsrArgs ir;
+  JgCommitArgs cm;
+};
+
+// rows k0 .. k0 + JG_POLL_FLIGHT - 1 of a tile: c[x] += the slots of feed x (leaders, replicas, commits) that differ from
+// its shadow, wave-uniform; bc / commits / appends: the commit backlog as k_commit_count keeps it
+template <bool L, bool I, bool C>
+__device__ __forceinline__ void jg_poll_rows(const JgDev& d, const JgPollArgs& a, uint32_t g0, uint32_t n, uint32_t tile, uint32_t k0,
+                                             uint32_t leave32, uint32_t join32, uint32_t lane, uint32_t* c, uint32_t* bc, uint64_t& commits,
+                                             uint64_t& appends) {
+  const uint32_t t0 = tile * JG_POLL_TILE + k0 * JG_BLOCK + threadIdx.x;
+  const uint32_t R = d.R;
+  uint32_t f[JG_POLL_FLIGHT], ish[JG_POLL_FLIGHT];
+  uint64_t term[JG_POLL_FLIGHT], w[JG_POLL_FLIGHT], head[JG_POLL_FLIGHT], col[JG_POLL_FLIGHT];
+  uint4 cold[JG_POLL_FLIGHT], lsh[JG_POLL_FLIGHT], csh[JG_POLL_FLIGHT];
+#pragma unroll
+  for (uint32_t k = 0; k < JG_POLL_FLIGHT; k++) {
+    const uint32_t i = t0 + k * JG_BLOCK;
+    const bool in = i < n;
+    const uint32_t g = g0 + (in ? i : 0u);
+    f[k] = in ? d.flags[g] : 0u;
+    if (L) {
+      term[k] = in ? d.term[g] : 0ull;
+      cold[k] = in ? d.cold.v[g] : make_uint4(0, 0, 0, 0);
+      lsh[k] = in ? a.lw.shadow[g] : make_uint4(0, 0, 0, 0);
+    }
+    if (I || C) w[k] = in ? d.mlag[g] : 0ull;
+    if (I) ish[k] = in ? a.ir.shadow[g] : 0u;
+    if (C) {
+      head[k] = in ? d.head[g] : 0ull;
+      col[k] = in ? d.commit[g] : 0ull;
+      csh[k] = in ? a.cm.shadow[g] : make_uint4(0, 0, 0, 0);
+    }
+  }
+  // (the loads stay up there: without an unconditional use the compiler sinks one behind a branch on the role)
+#pragma unroll
+  for (uint32_t k = 0; k < JG_POLL_FLIGHT; k++) {
+    asm volatile("" ::"v"(f[k]));
+    if (L) asm volatile("" ::"v"(term[k]), "v"(cold[k].y), "v"(lsh[k].x), "v"(lsh[k].z));
+    if (I || C) asm volatile("" ::"v"(w[k]));
+    if (I) asm volatile("" ::"v"(ish[k]));
+    if (C) asm volatile("" ::"v"(head[k]), "v"(col[k]), "v"(csh[k].x), "v"(csh[k].z));
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < JG_POLL_FLIGHT; k++) {
+    const uint32_t i = t0 + k * JG_BLOCK;
+    const bool in = i < n;
+    if (L) {  // jg_watch_ballots
+      const JgLeadView v = jg_lead_view(d, f[k], term[k], cold[k].y);
+      const bool differs = lsh[k].x != (uint32_t)v.term || lsh[k].y != (uint32_t)(v.term >> 32) || lsh[k].z != v.leader_id ||
+                           lsh[k].w != (v.meta ^ JG_WATCH_VACANT_META);
+      c[0] += __popcll(__ballot(in && differs));
+    }
+    if (I) {  // jg_isr_ballots
+      const uint32_t v = in ? jg_isr_word(d, a.ir.leave_lag, a.ir.join_lag, leave32, join32, g0 + i, f[k], w[k], ish[k]) : 0u;
+      c[1] += __popcll(__ballot(in && v != ish[k]));
+    }
+    if (C) {  // jg_commit_ballots, and the backlog of k_commit_count
+      const bool leader = (f[k] & JGF_ROLE_MASK) == JG_ROLE_LEADER;
+      const uint64_t fc = jg_lag_field(w[k], R, R);
+      uint64_t cm = leader ? head[k] - fc : col[k];  // the common case: a leader's commit IS head - field
+      if (leader && (jg_lag_wide(fc, R) || jg_lag_base_is_run_hi(f[k]))) cm = jg_read_commit(d, g0 + (in ? i : 0u), f[k]);  // rare: exact
+      const bool differs = csh[k].x != (uint32_t)cm || csh[k].y != (uint32_t)(cm >> 32) ||
+                           (!a.cm.commits_only && (csh[k].z != (uint32_t)head[k] || csh[k].w != (uint32_t)(head[k] >> 32)));
+      const uint64_t m = __ballot(in && differs);
+      c[2] += __popcll(m);
+      if (a.cm.backlog) {  // (uniform over the launch)
+        const bool on = (m >> lane) & 1ull;
+        const uint64_t cf = jg_cmt_u64(csh[k].x, csh[k].y), hf = jg_cmt_u64(csh[k].z, csh[k].w);
+        const bool up_c = on && cm > cf, up_h = on && head[k] > hf;
+        bc[0] += __popcll(m);
+        bc[1] += __popcll(__ballot(up_c));
+        bc[2] += __popcll(__ballot(up_h));
+        bc[3] += __popcll(__ballot(on && (cm < cf || head[k] < hf)));
+        commits += up_c ? cm - cf : 0ull;
+        appends += up_h ? head[k] - hf : 0ull;
+      }
+    }
+  }
+}
+
+template <bool L, bool I, bool C>
+__global__ __launch_bounds__(JG_BLOCK) void k_poll_count(JgDev d, JgPollArgs a) {
+  __shared__ uint32_t wave_n[3][JG_BLOCK / 64];
+  __shared__ uint64_t wave_b[JG_BLOCK / 64][JG_CMT_WORDS];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t g0 = L ? a.lw.g0 : a.ir.g0, n = L ? a.lw.n : a.ir.n;  // (two feeds at least: one of these is wanted)
+  const uint32_t leave32 = a.ir.leave_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.ir.leave_lag;
+  const uint32_t join32 = a.ir.join_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.ir.join_lag;
+  uint32_t bc[4] = {0u, 0u, 0u, 0u};  // changed, committed, appended, rewound: wave-uniform
+  uint64_t commits = 0, appends = 0;  // per lane
+  for (uint32_t tile = blockIdx.x; tile < a.tiles; tile += a.parts) {  // (uniform over the workgroup)
+    uint32_t c[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t k0 = 0; k0 < JG_POLL_ROWS; k0 += JG_POLL_FLIGHT)
+      jg_poll_rows<L, I, C>(d, a, g0, n, tile, k0, leave32, join32, lane, c, bc, commits, appends);
+    if (lane == 0) {
+#pragma unroll
+      for (uint32_t x = 0; x < 3; x++) wave_n[x][wave] = c[x];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {  // thread x: feed x's count of the tile
+      const uint32_t x = threadIdx.x;
+      uint32_t t = 0;
+#pragma unroll
+      for (uint32_t y = 0; y < JG_BLOCK / 64; y++) t += wave_n[x][y];
+      if (L && x == 0) a.lw.cnt[tile] = t, a.lw.bsum[tile] = t;
+      if (I && x == 1) a.ir.cnt[tile] = t, a.ir.bsum[tile] = t;
+      if (C && x == 2) a.cm.cnt[tile] = t, a.cm.bsum[tile] = t;
+    }
+    __syncthreads();  // (wave_n is the next tile's too)
+  }
+  if (!C || !a.cm.backlog) return;
+  commits = jg_wave_sum64(commits);
+  appends = jg_wave_sum64(appends);
+  if (lane == 0) {
+#pragma unroll
+    for (uint32_t x = 0; x < 4; x++) wave_b[wave][x] = bc[x];
+    wave_b[wave][4] = commits;
+    wave_b[wave][5] = appends;
+  }
+  __syncthreads();
+  if (threadIdx.x < JG_CMT_WORDS) {
+    uint64_t t = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < JG_BLOCK / 64; x++) t += wave_b[x][threadIdx.x];
+    a.cm.part[(size_t)blockIdx.x * JG_CMT_WORDS + threadIdx.x] = t;
+  }
+}

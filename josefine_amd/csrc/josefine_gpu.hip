@@ -33,6 +33,7 @@
 #include "jg_isr.h"
 #include "jg_lookup.h"
 #include "jg_commits.h"
+#include "jg_poll.h"
 
 // The host side, by entry-point family (ONE translation unit: the pieces see each other's internals, in this order)
 #include "jg_api_core.h"
@@ -51,3 +52,4 @@
 #include "jg_api_isr.h"
 #include "jg_api_lookup.h"
 #include "jg_api_commits.h"
+#include "jg_api_poll.h"

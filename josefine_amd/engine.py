@@ -784,6 +784,87 @@ class BatchedRaft(_Hosting):
             return rows, int(total.value)
         return rows, int(total.value), {name: int(getattr(b, name)) for name, _ in capi.CommitBacklog._fields_}
 
+    def poll(self, leaders=None, replicas=None, commits=None, census: bool = False, repl_census: Optional[int] = None,
+             g0: int = 0, n: Optional[int] = None) -> dict:
+        """jg_engine_poll: the parts asked for of one tick over the slots g0 .. g0 + n - 1 in ONE call - one settle, one
+        device pass, one synchronisation - each exactly as its separate method answers it.  A feed argument is None (not
+        asked: its shadow is not touched), True, or that feed's options as a dict or a tuple in this order:
+        leaders (limit, peek); replicas (leave_lag, join_lag, limit, peek); commits (limit, peek, commits_only, backlog).
+        `census`: jg_engine_census too; `repl_census`: the lag limit of jg_engine_replication_census, or None.  Returns a
+        dict keyed by the parts asked for: "leaders" / "replicas" (rows, total), "commits" (rows, total) or with backlog
+        (rows, total, backlog), "census" / "repl_census" the dicts of census() / replication_census()."""
+        n = self.G - int(g0) if n is None else int(n)
+        if not hasattr(self.api, "engine_poll"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_poll")
+
+        def options(arg, names, defaults):
+            if arg is True:
+                arg = {}
+            if not isinstance(arg, dict):
+                arg = dict(zip(names, tuple(arg)))
+            unknown = set(arg) - set(names)
+            if unknown:
+                raise TypeError(f"poll: unknown option {sorted(unknown)}")
+            return {**defaults, **arg}
+
+        def rows_of(limit, dtype):
+            cap = n if limit is None else max(0, min(int(limit), n))
+            return cap, np.zeros(max(cap, 1), dtype)
+
+        p = capi.Poll()
+        p.g0, p.n = int(g0), n
+        keep = {}
+        if leaders is not None:
+            o = options(leaders, ("limit", "peek"), dict(limit=None, peek=False))
+            p.want |= capi.POLL_LEADERS
+            p.leader_flags = capi.WATCH_PEEK if o["peek"] else 0
+            p.leaders_cap, keep["leaders"] = rows_of(o["limit"], capi.LEADER_ROW_DTYPE)
+            p.leaders = keep["leaders"].ctypes.data
+        if replicas is not None:
+            o = options(replicas, ("leave_lag", "join_lag", "limit", "peek"), dict(join_lag=None, limit=None, peek=False))
+            p.want |= capi.POLL_REPLICAS
+            p.replica_flags = capi.WATCH_PEEK if o["peek"] else 0
+            p.policy = capi.IsrPolicy(int(o["leave_lag"]), int(o["leave_lag"] if o["join_lag"] is None else o["join_lag"]))
+            p.replicas_cap, keep["replicas"] = rows_of(o["limit"], capi.ISR_ROW_DTYPE)
+            p.replicas = keep["replicas"].ctypes.data
+        backlog = False
+        if commits is not None:
+            o = options(commits, ("limit", "peek", "commits_only", "backlog"), dict(limit=None, peek=False, commits_only=False, backlog=False))
+            p.want |= capi.POLL_COMMITS
+            p.commit_flags = (capi.WATCH_PEEK if o["peek"] else 0) | (capi.WATCH_COMMITS_ONLY if o["commits_only"] else 0)
+            p.commits_cap, keep["commits"] = rows_of(o["limit"], capi.COMMIT_ROW_DTYPE)
+            p.commits = keep["commits"].ctypes.data
+            backlog = bool(o["backlog"])
+        b, c, rc = capi.CommitBacklog(), capi.Census(), capi.ReplCensus()
+        if backlog:
+            p.backlog = C.pointer(b)
+        if census:
+            p.want |= capi.POLL_CENSUS
+            p.census = C.pointer(c)
+        if repl_census is not None:
+            p.want |= capi.POLL_REPL_CENSUS
+            p.census_lag_limit = int(repl_census)
+            p.repl_census = C.pointer(rc)
+        self._check(self.api.engine_poll(self._h, C.byref(p)))
+        out = {}
+        if leaders is not None:
+            out["leaders"] = keep["leaders"][:min(p.leaders_cap, p.leaders_total)], int(p.leaders_total)
+        if replicas is not None:
+            out["replicas"] = keep["replicas"][:min(p.replicas_cap, p.replicas_total)], int(p.replicas_total)
+        if commits is not None:
+            out["commits"] = keep["commits"][:min(p.commits_cap, p.commits_total)], int(p.commits_total)
+            if backlog:
+                out["commits"] += ({name: int(getattr(b, name)) for name, _ in capi.CommitBacklog._fields_},)
+        if census:
+            out["census"] = {name: int(getattr(c, name)) for name, t in capi.Census._fields_ if name != "led_by"}
+            out["census"]["led_by"] = [int(x) for x in c.led_by[:self.R]]
+        if repl_census is not None:
+            per_member = ("out_of_sync", "max_lag", "sum_lag")
+            out["repl_census"] = {name: int(getattr(rc, name)) for name, t in capi.ReplCensus._fields_ if name not in per_member}
+            for name in per_member:
+                out["repl_census"][name] = [int(x) for x in getattr(rc, name)[:self.R]]
+        return out
+
     def counters(self) -> dict:
         arr = (C.c_uint64 * 4)()
         self._check(self.api.get_counters(self._h, C.byref(arr)))

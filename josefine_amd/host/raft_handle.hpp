@@ -373,6 +373,51 @@ class BatchedRaft {
     if (total) *total = tot;
     return out;
   }
+  // One poll per tick (jg_engine_poll, ABI v18; only callers need a library that has it): the parts `want` names of
+  // watch_leaders, watch_replicas, watch_commits, census and replication_census over [g0, g0 + n) in ONE call - one settle,
+  // one device pass over the slots, one synchronisation - each exactly as its own call answers it, the shadows shared with
+  // them.  A part not named is neither computed nor advanced.  Read the answers in the order leaders, replicas, commits: a
+  // role change is known before the ranges of the commit rows are applied.
+  struct PollRequest {
+    uint32_t want = JG_POLL_LEADERS | JG_POLL_REPLICAS | JG_POLL_COMMITS;
+    uint32_t g0 = 0, n = UINT32_MAX;
+    size_t leaders_limit = SIZE_MAX, replicas_limit = SIZE_MAX, commits_limit = SIZE_MAX;
+    bool leaders_peek = false, replicas_peek = false, commits_peek = false;
+    bool commits_only = false;
+    jg_isr_policy policy{0, 0};    // JG_POLL_REPLICAS
+    uint64_t census_lag_limit = 0;  // JG_POLL_REPL_CENSUS
+  };
+  struct PollResult {
+    std::vector<jg_leader_row> leaders;
+    std::vector<jg_isr_row> replicas;
+    std::vector<jg_commit_row> commits;
+    size_t leaders_total = 0, replicas_total = 0, commits_total = 0;
+    jg_commit_backlog backlog{};
+    jg_census census{};
+    jg_repl_census repl_census{};
+  };
+  PollResult poll(const PollRequest& q) {
+    PollResult r;
+    jg_poll p{};
+    p.want = q.want, p.g0 = q.g0, p.n = q.n == UINT32_MAX ? (uint32_t)stores_.size() - q.g0 : q.n;
+    p.leader_flags = q.leaders_peek ? (uint32_t)JG_WATCH_PEEK : 0u;
+    p.replica_flags = q.replicas_peek ? (uint32_t)JG_WATCH_PEEK : 0u;
+    p.commit_flags = (q.commits_peek ? (uint32_t)JG_WATCH_PEEK : 0u) | (q.commits_only ? (uint32_t)JG_WATCH_COMMITS_ONLY : 0u);
+    p.policy = q.policy, p.census_lag_limit = q.census_lag_limit;
+    if (q.want & JG_POLL_LEADERS) r.leaders.resize(std::min<size_t>(q.leaders_limit, p.n));
+    if (q.want & JG_POLL_REPLICAS) r.replicas.resize(std::min<size_t>(q.replicas_limit, p.n));
+    if (q.want & JG_POLL_COMMITS) r.commits.resize(std::min<size_t>(q.commits_limit, p.n));
+    p.leaders = r.leaders.data(), p.leaders_cap = r.leaders.size();
+    p.replicas = r.replicas.data(), p.replicas_cap = r.replicas.size();
+    p.commits = r.commits.data(), p.commits_cap = r.commits.size();
+    p.backlog = &r.backlog, p.census = &r.census, p.repl_census = &r.repl_census;
+    check(jg_engine_poll(e_, &p));
+    r.leaders_total = p.leaders_total, r.replicas_total = p.replicas_total, r.commits_total = p.commits_total;
+    r.leaders.resize(std::min<size_t>(r.leaders_total, r.leaders.size()));
+    r.replicas.resize(std::min<size_t>(r.replicas_total, r.replicas.size()));
+    r.commits.resize(std::min<size_t>(r.commits_total, r.commits.size()));
+    return r;
+  }
   // commit rows as the FSM rows a dense step does not queue: every row that is COMMITTED and not REWOUND becomes
   // JG_FSM_APPLY_LEADER (where LEADS: keys (a, b]) or JG_FSM_APPLY_FOLLOWER (keys [a, b)) {a = commit_from, b = commit}; a
   // rewound row has no range - the consumer resynchronises its store from the row's commit / head
