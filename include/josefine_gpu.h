@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 18u /* v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 19u /* v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -575,6 +575,58 @@ typedef struct jg_repl_census {
 } jg_repl_census;
 int jg_engine_watch_replicas(jg_engine* e, uint32_t flags, const jg_isr_policy* p, uint32_t g0, uint32_t n, jg_isr_row* out, size_t cap, size_t* total);
 int jg_engine_replication_census(jg_engine* e, uint64_t lag_limit, uint32_t g0, uint32_t n, jg_repl_census* out);
+
+/* ---- the replication feed under the time rule (ABI v19) ----------------------------------------------
+ * replica.lag.time.max.ms: a member leaves the in-sync set once it has been BEHIND for longer than
+ * max_behind_ms, not once it is some number of blocks behind - a block threshold has no right value (low, a
+ * bursty producer evicts healthy followers; high, a dead follower of a slow partition is never noticed).
+ *
+ * jg_engine_watch_replicas_timed is jg_engine_watch_replicas under another membership rule: the rows, the
+ * `state` bits, replicate / head / worst_lag, the ascending order, cap, total and JG_WATCH_PEEK are the
+ * same, and it shares the SHADOW - the (isr, LEADS) last delivered - with it: ONE feed, so the two calls
+ * and jg_engine_poll may be mixed.  New is one piece of feed memory, the CLOCKS, allocated zero-filled at
+ * the first timed call: stamp[r][g], 8 bytes per member and slot; 0 = "not behind at the last sample", any
+ * other value = now_ms + 1 of the first sample that saw the member behind.
+ *
+ * Per slot g of the range, lag_r as above (saturating) and was_r from the shadow:
+ *   - the slot does not lead (role != leader, or fault != 0, or vacant): the view is 0 and every clock of
+ *     the slot becomes 0
+ *   - it leads, own slot s: bit s is set, its clock is ignored
+ *   - it leads, member r != s:
+ *       c'        = lag_r <= caught_lag ? 0 : (stamp ? stamp : now_ms + 1)
+ *       behind_ms = c' ? (now_ms + 1 > c' ? now_ms + 1 - c' : 0) : 0     (saturating: a clock that steps
+ *                   back evicts nobody)
+ *       in_r      = was_r ? behind_ms <= max_behind_ms : lag_r <= join_lag
+ *   - isr, state and "differs from the shadow" are then as in the lag feed
+ * A call WITHOUT JG_WATCH_PEEK stores stamp := c' (or 0) for EVERY slot of g0 .. g0 + n - 1, whether or not
+ * the slot's row fits cap and whether or not it differs: time passes for a row that was not delivered.
+ * Advancing twice at one now_ms on unchanged state is idempotent.  The shadow advances for exactly the
+ * delivered slots, as in the lag feed.  A call WITH JG_WATCH_PEEK computes with c' and writes neither clocks
+ * nor shadow.
+ *
+ * What follows from that:
+ *   - the clock is SAMPLED: its resolution is the poll period, and a member is never seen behind for
+ *     longer than the samples show
+ *   - a follower already down at the first timed call leaves max_behind_ms after that call
+ *   - a slot that stops leading and leads again between two samples keeps its clocks, as it keeps its shadow
+ *   - under continuous appends a follower that is always a few blocks behind is "behind" at every sample:
+ *     caught_lag has to be at least what is in flight per sample
+ *   - max_behind_ms = UINT64_MAX: nobody ever leaves; 0: a member leaves at the first sample after the
+ *     one that saw it fall behind, provided the clock has moved
+ *
+ * It READS under the rules of jg_engine_watch_replicas and is refused with JG_EINVAL - nothing written, no
+ * clock and no shadow advanced - wherever that call is (a null `e` / `total`, a null `out` with cap > 0, an
+ * unknown flag, a range out of bounds, kept node steps outstanding), for a null clock, now_ms ==
+ * UINT64_MAX and join_lag > caught_lag.  n = 0 is JG_OK with total 0.  A multi-device parent handle answers
+ * in global slot order with `cap` over the whole answer; without JG_WATCH_PEEK the clocks of EVERY shard
+ * advance, those behind the point where cap ran out too.  jg_engine_poll keeps the lag rule. */
+typedef struct jg_isr_clock {
+  uint64_t now_ms;         /* the caller's clock at this sample; UINT64_MAX is refused            */
+  uint64_t max_behind_ms;  /* replica.lag.time.max.ms; UINT64_MAX: never leaves                   */
+  uint64_t caught_lag;     /* a member with lag <= this is "caught up" at this sample (0 = strict) */
+  uint64_t join_lag;       /* a member outside the set joins at lag <= this; join_lag <= caught_lag */
+} jg_isr_clock;
+int jg_engine_watch_replicas_timed(jg_engine* e, uint32_t flags, const jg_isr_clock* c, uint32_t g0, uint32_t n, jg_isr_row* out, size_t cap, size_t* total);
 
 /* ---- point queries: the state of a list of partitions (ABI v16) --------------------------------------
  * "What is the state of exactly these partitions" - Metadata for some topics, the high watermark of the

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -230,6 +230,11 @@ class IsrPolicy(C.Structure):
     _fields_ = [("leave_lag", C.c_uint64), ("join_lag", C.c_uint64)]
 
 
+class IsrClock(C.Structure):
+    """jg_isr_clock."""
+    _fields_ = [("now_ms", C.c_uint64), ("max_behind_ms", C.c_uint64), ("caught_lag", C.c_uint64), ("join_lag", C.c_uint64)]
+
+
 # jg_commit_row.state
 CMT_COMMITTED, CMT_APPENDED, CMT_REWOUND, CMT_LEADS, CMT_VACANT, CMT_FAULTED = 1, 2, 4, 8, 16, 32
 
@@ -390,6 +395,8 @@ class Api:
         "engine_watch_replicas": (C.c_int, [_P, C.c_uint32, C.POINTER(IsrPolicy), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                             C.POINTER(C.c_size_t)]),
         "engine_replication_census": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(ReplCensus)]),
+        "engine_watch_replicas_timed": (C.c_int, [_P, C.c_uint32, C.POINTER(IsrClock), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                  C.POINTER(C.c_size_t)]),
         "engine_lookup_groups": (C.c_int, [_P, C.POINTER(GroupSet), C.c_void_p, C.c_void_p]),
         "engine_watch_commits": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                            C.POINTER(CommitBacklog)]),
@@ -442,4 +449,5 @@ HEADER_SYMBOLS = [
     "jg_engine_lookup_groups",
     "jg_engine_watch_commits",
     "jg_engine_poll",
+    "jg_engine_watch_replicas_timed",
 ]

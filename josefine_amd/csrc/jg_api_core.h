@@ -286,6 +286,10 @@ struct jg_engine {
   // jg_engine_watch_replicas: the in-sync set last reported per slot ([G] words of jg_isr.h, zero = "not leading, empty");
   // allocated at the first watch
   uint32_t* isr_shadow = nullptr;
+  // jg_engine_watch_replicas_timed: the clocks of jg_isr_clock.h - [R][G] stamps (zero = "not behind at the last sample")
+  // and their [G] mask bytes (bit r = stamp[r][g] != 0); allocated at the first timed watch, freed with the shadow
+  uint64_t* isr_stamp = nullptr;
+  uint8_t* isr_behind = nullptr;
   // jg_engine_watch_commits: the (commit, head) last delivered per slot ([G] records of jg_commits.h, zero = "genesis
   // only"); allocated at the first watch
   uint4* commit_shadow = nullptr;

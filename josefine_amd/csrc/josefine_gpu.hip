@@ -31,6 +31,7 @@
 #include "jg_hosting.h"
 #include "jg_watch.h"
 #include "jg_isr.h"
+#include "jg_isr_clock.h"
 #include "jg_lookup.h"
 #include "jg_commits.h"
 #include "jg_poll.h"
@@ -50,6 +51,7 @@
 #include "jg_api_hosting.h"
 #include "jg_api_watch.h"
 #include "jg_api_isr.h"
+#include "jg_api_isr_clock.h"
 #include "jg_api_lookup.h"
 #include "jg_api_commits.h"
 #include "jg_api_poll.h"

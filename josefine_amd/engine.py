@@ -723,6 +723,24 @@ class BatchedRaft(_Hosting):
         self._check(self.api.engine_watch_replicas(self._h, flags, C.byref(pol), int(g0), n, out.ctypes.data, cap, C.byref(total)))
         return out[:min(cap, total.value)], int(total.value)
 
+    def watch_replicas_timed(self, now_ms: int, max_behind_ms: int, caught_lag: int = 0, join_lag: int = 0, g0: int = 0,
+                             n: Optional[int] = None, limit: Optional[int] = None, peek: bool = False):
+        """jg_engine_watch_replicas_timed: watch_replicas under the time rule (replica.lag.time.max.ms) - the same feed, the
+        same rows and the same shadow, (rows, total).  A member the feed last reported in sync stays until it has been behind
+        (lag > caught_lag) for more than max_behind_ms of the caller's clock, sampled at the calls; any other joins at lag <=
+        join_lag (<= caught_lag).  Unless `peek`, the clocks of EVERY slot of the range advance to now_ms, delivered or not,
+        and the delivered slots become "seen"; `peek` delivers the same rows and advances neither."""
+        n = self.G - int(g0) if n is None else int(n)
+        if not hasattr(self.api, "engine_watch_replicas_timed"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_watch_replicas_timed")
+        cap = n if limit is None else max(0, min(int(limit), n))
+        out = np.zeros(max(cap, 1), capi.ISR_ROW_DTYPE)
+        total = C.c_size_t(0)
+        clk = capi.IsrClock(int(now_ms), int(max_behind_ms), int(caught_lag), int(join_lag))
+        flags = capi.WATCH_PEEK if peek else 0
+        self._check(self.api.engine_watch_replicas_timed(self._h, flags, C.byref(clk), int(g0), n, out.ctypes.data, cap, C.byref(total)))
+        return out[:min(cap, total.value)], int(total.value)
+
     def replication_census(self, lag_limit: int, g0: int = 0, n: Optional[int] = None) -> dict:
         """jg_engine_replication_census over the slots g0 .. g0 + n - 1 with the one threshold lag_limit: a dict of
         jg_repl_census's fields (out_of_sync / max_lag / sum_lag: lists of R values, one per member slot)."""

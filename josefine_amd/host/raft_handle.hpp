@@ -324,6 +324,20 @@ class BatchedRaft {
     if (total) *total = tot;
     return out;
   }
+  // ... under the time rule (jg_engine_watch_replicas_timed, ABI v19; only callers need a library that has it): the same
+  // feed and the same shadow, but a member last reported in sync stays until it has been behind (lag > clock.caught_lag) for
+  // more than clock.max_behind_ms - replica.lag.time.max.ms - of the caller's clock clock.now_ms, sampled at the calls; any
+  // other joins at lag <= clock.join_lag.  Unless `peek` the clocks of every slot of the range advance, delivered or not.
+  std::vector<jg_isr_row> watch_replicas_timed(jg_isr_clock clock, uint32_t g0 = 0, uint32_t n = UINT32_MAX, size_t limit = SIZE_MAX,
+                                               bool peek = false, size_t* total = nullptr) {
+    if (n == UINT32_MAX) n = (uint32_t)stores_.size() - g0;
+    std::vector<jg_isr_row> out(std::min<size_t>(limit, n));
+    size_t tot = 0;
+    check(jg_engine_watch_replicas_timed(e_, peek ? (uint32_t)JG_WATCH_PEEK : 0u, &clock, g0, n, out.data(), out.size(), &tot));
+    out.resize(std::min<size_t>(tot, out.size()));
+    if (total) *total = tot;
+    return out;
+  }
   jg_repl_census replication_census(uint64_t lag_limit, uint32_t g0 = 0, uint32_t n = UINT32_MAX) {
     if (n == UINT32_MAX) n = (uint32_t)stores_.size() - g0;
     jg_repl_census c{};
