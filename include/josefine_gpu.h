@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 19u /* v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 20u /* v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -619,7 +619,7 @@ int jg_engine_replication_census(jg_engine* e, uint64_t lag_limit, uint32_t g0, 
  * unknown flag, a range out of bounds, kept node steps outstanding), for a null clock, now_ms ==
  * UINT64_MAX and join_lag > caught_lag.  n = 0 is JG_OK with total 0.  A multi-device parent handle answers
  * in global slot order with `cap` over the whole answer; without JG_WATCH_PEEK the clocks of EVERY shard
- * advance, those behind the point where cap ran out too.  jg_engine_poll keeps the lag rule. */
+ * advance, those behind the point where cap ran out too. */
 typedef struct jg_isr_clock {
   uint64_t now_ms;         /* the caller's clock at this sample; UINT64_MAX is refused            */
   uint64_t max_behind_ms;  /* replica.lag.time.max.ms; UINT64_MAX: never leaves                   */
@@ -744,28 +744,42 @@ int jg_engine_watch_commits(jg_engine* e, uint32_t flags, uint32_t g0, uint32_t 
  * of 104), one scan launch and ONE synchronisation.  It defines no value of its own:
  *
  * CONTRACT.  Let S be the separate calls that `want` names - jg_engine_watch_leaders (JG_POLL_LEADERS:
- * leader_flags, leaders, leaders_cap, leaders_total), jg_engine_watch_replicas (JG_POLL_REPLICAS:
- * replica_flags, policy, replicas, replicas_cap, replicas_total), jg_engine_watch_commits
+ * leader_flags, leaders, leaders_cap, leaders_total), jg_engine_watch_replicas (JG_POLL_REPLICAS with
+ * clock == NULL: replica_flags, policy, replicas, replicas_cap, replicas_total) or, since v20,
+ * jg_engine_watch_replicas_timed (JG_POLL_REPLICAS with clock != NULL: replica_flags, clock, replicas,
+ * replicas_cap, replicas_total; policy is then not read), jg_engine_watch_commits
  * (JG_POLL_COMMITS: commit_flags, commits, commits_cap, commits_total, backlog - may be NULL),
  * jg_engine_census (JG_POLL_CENSUS: census), jg_engine_replication_census (JG_POLL_REPL_CENSUS:
  * census_lag_limit, repl_census) - each over local slots g0 .. g0 + n - 1.  The poll leaves exactly what
  * S leaves when each is called on the same engine state: every output byte, every total, the backlog,
- * and the three shadows.  The feeds do not observe each other, so no order among the parts is defined.
+ * the three shadows and the replication feed's clocks (the stamps and their mask).  Under the time rule
+ * and without JG_WATCH_PEEK in replica_flags the clocks of EVERY slot of the range advance to
+ * clock->now_ms, delivered or not and whatever replicas_cap is, 0 included; with JG_WATCH_PEEK neither
+ * clocks nor shadow are written.  *clock is copied at entry.  JG_POLL_REPL_CENSUS stays the lag gauge of
+ * census_lag_limit whichever rule the feed runs under.  The feeds do not observe each other, so no order
+ * among the parts is defined.
  * A part NOT named is not computed: its shadow is neither allocated nor advanced and its fields of
- * jg_poll are neither read nor written.  The poll and the separate calls share the shadows and may be
- * mixed freely on one engine.
+ * jg_poll are neither read nor written (clock is not dereferenced unless JG_POLL_REPLICAS is wanted).
+ * The lag poll, the timed poll, jg_engine_watch_replicas and jg_engine_watch_replicas_timed share one
+ * shadow and one set of clocks; the poll and the separate calls may be mixed freely on one engine.
  *
  * ALL OR NOTHING.  Every argument of every wanted part is checked before anything is queued, by the
- * separate calls' own rules: JG_EINVAL - no shadow advanced, no byte of any output or total written - for
- * a null `e` / `p`, want == 0 or an unknown bit, an unknown flag in a wanted feed's flag word, join_lag >
- * leave_lag, a null row array with a nonzero cap, a null census pointer of a wanted census, a range out
+ * separate calls' own rules: JG_EINVAL - no shadow and no clock advanced, no byte of any output or total
+ * written - for a null `e` / `p`, want == 0 or an unknown bit, an unknown flag in a wanted feed's flag
+ * word, join_lag > leave_lag in the policy of a wanted replicas part without a clock, now_ms ==
+ * UINT64_MAX or join_lag > caught_lag in the clock of a wanted replicas part (the policy is then not
+ * looked at: join_lag > leave_lag in it is no error), a null row array with a nonzero cap, a null census pointer of a wanted census, a range out
  * of bounds, kept node steps outstanding.  n == 0 is JG_OK with totals 0 and zeroed censuses and backlog.
  *
  * It READS: JG_NODE_ASYNC steps are settled once; nothing a step, a drain, jg_read_state or a separate
  * feed call can observe changes, the shadows as stated above excepted.  A multi-device parent handle
  * sizes every shard by one fused peek that delivers nothing (the backlog and the censuses are the shards'
  * sums or maxima from that pass), then each shard delivers into what is left of EACH feed's own cap, in
- * global slot order; a shard behind the point where a feed's cap ran out keeps that feed's shadow. */
+ * global slot order; a shard behind the point where a feed's cap ran out keeps that feed's shadow.
+ * Under the time rule the sizing pass is no peek of the replicas part: it delivers nothing and, unless the
+ * caller peeks, advances that shard's clocks; the delivering pass advances them again at the same now_ms,
+ * which is idempotent.  A shard behind the point where the replicas' cap ran out keeps its shadow, and its
+ * clocks have advanced. */
 enum { JG_POLL_LEADERS = 1u, JG_POLL_REPLICAS = 2u, JG_POLL_COMMITS = 4u,
        JG_POLL_CENSUS = 8u, JG_POLL_REPL_CENSUS = 16u };   /* jg_poll.want */
 typedef struct jg_poll {
@@ -785,6 +799,7 @@ typedef struct jg_poll {
   jg_commit_backlog* backlog;          /* out, may be NULL                                       */
   jg_census* census;                   /* out: JG_POLL_CENSUS                                    */
   jg_repl_census* repl_census;         /* out: JG_POLL_REPL_CENSUS                               */
+  const jg_isr_clock* clock;           /* JG_POLL_REPLICAS: NULL = the lag rule (policy); else the time rule, policy is not read */
 } jg_poll;
 int jg_engine_poll(jg_engine* e, jg_poll* p);
 

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -262,7 +262,8 @@ class Poll(C.Structure):
                 ("leaders", C.c_void_p), ("leaders_cap", C.c_size_t), ("leaders_total", C.c_size_t),
                 ("replicas", C.c_void_p), ("replicas_cap", C.c_size_t), ("replicas_total", C.c_size_t),
                 ("commits", C.c_void_p), ("commits_cap", C.c_size_t), ("commits_total", C.c_size_t),
-                ("backlog", C.POINTER(CommitBacklog)), ("census", C.POINTER(Census)), ("repl_census", C.POINTER(ReplCensus))]
+                ("backlog", C.POINTER(CommitBacklog)), ("census", C.POINTER(Census)), ("repl_census", C.POINTER(ReplCensus)),
+                ("clock", C.POINTER(IsrClock))]
 
 
 # mailbox words (josefine_gpu.h: JG_ANSWER / JG_AE)

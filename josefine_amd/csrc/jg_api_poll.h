@@ -13,13 +13,17 @@ enum { POLL_L = 0, POLL_I = 1, POLL_C = 2 };  // the feeds in the order a consum
 
 // one single-device engine's part of a poll: shard-local slots [g0, g0 + n); per wanted feed x the first cap[x] changed
 // rows (groups + add) into host out[x], their shadow advanced unless peek[x], total[x] the slots that differ; the parts not
-// wanted are neither computed nor touched
+// wanted are neither computed nor touched.  With `timed` the replicas part is under the time rule of `clk` (pol is not
+// read), and peek[POLL_I] says two things: the shadow of the delivered rows is left alone, as for the other feeds, AND the
+// clocks of the range are - without it they advance to clk.now_ms whatever cap[POLL_I] is, 0 included
 struct PollShard {
   uint32_t want = 0;  // JG_POLL_*
   uint32_t g0 = 0, n = 0, add = 0;
   bool peek[3] = {false, false, false};
   bool commits_only = false;
   jg_isr_policy pol{};
+  bool timed = false;
+  jg_isr_clock clk{};
   uint64_t lag_limit = 0;
   void* out[3] = {nullptr, nullptr, nullptr};
   size_t cap[3] = {0, 0, 0}, total[3] = {0, 0, 0};
@@ -50,6 +54,11 @@ int poll_shard(jg_engine* e, PollShard& q) {
     if (const int rc = dev_alloc(e, &e->watch_shadow, e->cfg.n_groups)) return rc;
   if (on[POLL_I] && !e->isr_shadow)
     if (const int rc = dev_alloc(e, &e->isr_shadow, e->cfg.n_groups)) return rc;
+  const bool timed = on[POLL_I] && q.timed;
+  if (timed && !e->isr_stamp)  // (the clocks, as isr_clock_shard allocates them: no member was behind at the last sample)
+    if (const int rc = dev_alloc(e, &e->isr_stamp, (size_t)e->cfg.n_replicas * e->cfg.n_groups)) return rc;
+  if (timed && !e->isr_behind)
+    if (const int rc = dev_alloc(e, &e->isr_behind, e->cfg.n_groups)) return rc;
   if (on[POLL_C] && !e->commit_shadow)
     if (const int rc = dev_alloc(e, &e->commit_shadow, e->cfg.n_groups)) return rc;
   JgPollArgs a{};
@@ -84,6 +93,12 @@ int poll_shard(jg_engine* e, PollShard& q) {
   a.lw.out = (jg_leader_row*)(B + o_out[POLL_L]), a.ir.out = (jg_isr_row*)(B + o_out[POLL_I]), a.cm.out = (uint4*)(B + o_out[POLL_C]);
   a.lw.cap = wcap[POLL_L], a.ir.cap = wcap[POLL_I], a.cm.cap = wcap[POLL_C];
   a.ir.leave_lag = q.pol.leave_lag, a.ir.join_lag = q.pol.join_lag;
+  if (timed) {  // (the same feed: the shadow, the scratch and the rows are the lag rule's)
+    a.ic.g0 = q.g0, a.ic.n = q.n, a.ic.add = q.add, a.ic.peek = a.ir.peek;
+    a.ic.now1 = q.clk.now_ms + 1, a.ic.max_behind_ms = q.clk.max_behind_ms, a.ic.caught_lag = q.clk.caught_lag, a.ic.join_lag = q.clk.join_lag;
+    a.ic.shadow = e->isr_shadow, a.ic.stamp = e->isr_stamp, a.ic.mask = e->isr_behind;
+    a.ic.cnt = a.ir.cnt, a.ic.bsum = a.ir.bsum, a.ic.out = a.ir.out, a.ic.cap = a.ir.cap;
+  }
   a.cm.commits_only = q.commits_only ? 1u : 0u, a.cm.backlog = backlog ? 1u : 0u;
   a.cm.tiles = a.tiles, a.cm.parts = a.parts;
   a.cm.part = (uint64_t*)(B + o_part), a.cm.sum = (uint64_t*)(B + o_sum);
@@ -101,10 +116,18 @@ int poll_shard(jg_engine* e, PollShard& q) {
     // the count pass: ONE over the slots - a single feed's own, else the fused one of the feeds wanted
     if (feeds == 1 && on[POLL_L])
       hipLaunchKernelGGL(k_watch_count, dim3(a.tiles), block, 0, e->stream, e->dev, a.lw);
+    else if (feeds == 1 && timed)
+      hipLaunchKernelGGL(k_isrc_count, dim3(a.tiles), block, 0, e->stream, e->dev, a.ic);
     else if (feeds == 1 && on[POLL_I])
       hipLaunchKernelGGL(k_isr_count, dim3(a.tiles), block, 0, e->stream, e->dev, a.ir);
     else if (feeds == 1)
       hipLaunchKernelGGL(k_commit_count, grid, block, 0, e->stream, e->dev, a.cm);
+    else if (timed && !on[POLL_C])
+      hipLaunchKernelGGL((k_poll_count_timed<true, false>), grid, block, 0, e->stream, e->dev, a);
+    else if (timed && !on[POLL_L])
+      hipLaunchKernelGGL((k_poll_count_timed<false, true>), grid, block, 0, e->stream, e->dev, a);
+    else if (timed)
+      hipLaunchKernelGGL((k_poll_count_timed<true, true>), grid, block, 0, e->stream, e->dev, a);
     else if (!on[POLL_C])
       hipLaunchKernelGGL((k_poll_count<true, true, false>), grid, block, 0, e->stream, e->dev, a);
     else if (!on[POLL_I])
@@ -125,7 +148,10 @@ int poll_shard(jg_engine* e, PollShard& q) {
       e->n_launch++;
     }
     if (wcap[POLL_I]) {
-      hipLaunchKernelGGL(k_isr_write, dim3(a.tiles), block, 0, e->stream, e->dev, a.ir);
+      if (timed)
+        hipLaunchKernelGGL(k_isrc_write, dim3(a.tiles), block, 0, e->stream, e->dev, a.ic);
+      else
+        hipLaunchKernelGGL(k_isr_write, dim3(a.tiles), block, 0, e->stream, e->dev, a.ir);
       e->n_launch++;
     }
     if (wcap[POLL_C]) {
@@ -174,7 +200,11 @@ int jg_engine_poll(jg_engine* e, jg_poll* p) {
   if (on[POLL_I] && (p->replica_flags & ~(uint32_t)JG_WATCH_PEEK)) return fail(JG_EINVAL, "jg_engine_poll: unknown replica flag");
   if (on[POLL_C] && (p->commit_flags & ~(uint32_t)(JG_WATCH_PEEK | JG_WATCH_COMMITS_ONLY)))
     return fail(JG_EINVAL, "jg_engine_poll: unknown commit flag");
-  if (on[POLL_I] && p->policy.join_lag > p->policy.leave_lag) return fail(JG_EINVAL, "jg_engine_poll: join_lag above leave_lag");
+  const bool timed = on[POLL_I] && p->clock;  // (the clock of a replicas part that is not wanted is not dereferenced)
+  const jg_isr_clock clk = timed ? *p->clock : jg_isr_clock{};
+  if (timed && clk.now_ms == UINT64_MAX) return fail(JG_EINVAL, "jg_engine_poll: now_ms is UINT64_MAX");
+  if (timed && clk.join_lag > clk.caught_lag) return fail(JG_EINVAL, "jg_engine_poll: join_lag above caught_lag");
+  if (on[POLL_I] && !timed && p->policy.join_lag > p->policy.leave_lag) return fail(JG_EINVAL, "jg_engine_poll: join_lag above leave_lag");
   if ((on[POLL_L] && p->leaders_cap && !p->leaders) || (on[POLL_I] && p->replicas_cap && !p->replicas) ||
       (on[POLL_C] && p->commits_cap && !p->commits))
     return fail(JG_EINVAL, "jg_engine_poll: null rows with a cap");
@@ -192,6 +222,7 @@ int jg_engine_poll(jg_engine* e, jg_poll* p) {
   for (int x = 0; x < 3; x++) base.peek[x] = (fl[x] & JG_WATCH_PEEK) != 0;
   base.commits_only = (p->commit_flags & JG_WATCH_COMMITS_ONLY) != 0;
   base.pol = p->policy, base.lag_limit = p->census_lag_limit;
+  base.timed = timed, base.clk = clk;
   const size_t D = shard_count(e);
   std::vector<PollShard> q(D, base);
   std::vector<uint64_t> w(D * JG_CMT_WORDS, 0);
@@ -206,12 +237,15 @@ int jg_engine_poll(jg_engine* e, jg_poll* p) {
   } else {
     // a sharded handle: every shard is sized first by ONE fused peek that delivers nothing (the backlog and the censuses
     // are the shards' sums or maxima from that pass); then each shard delivers - and advances - into what is left of EACH
-    // feed's own cap behind the shards before it; a shard behind the point where a feed's cap ran out keeps that shadow
+    // feed's own cap behind the shards before it; a shard behind the point where a feed's cap ran out keeps that shadow.
+    // Under the time rule the sizing pass keeps the CALLER's peek for the replicas - it delivers nothing (cap 0) and, unless
+    // the caller peeks, advances that shard's clocks: time passes on every shard, those behind the cap too; the delivering
+    // pass advances them again at the same now_ms, which stores nothing
     int rc = each_shard(e, [&](size_t d) -> int {
       const ShardPart sp = shard_part(e, d, p->g0, p->n);
       PollShard& s = q[d];
       s.g0 = sp.g0, s.n = sp.n;
-      for (int x = 0; x < 3; x++) s.peek[x] = true;
+      for (int x = 0; x < 3; x++) s.peek[x] = x == POLL_I && timed ? base.peek[x] : true;
       s.backlog = backlog ? w.data() + d * JG_CMT_WORDS : nullptr;
       return poll_shard(shard_at(e, d), s);
     });

@@ -14,17 +14,25 @@
 //                          walks a tile of four rows as passes of JG_POLL_FLIGHT rows: every distinct column of the
 //                          wanted feeds loaded once, all of a pass's loads in flight before the first use; per feed and
 //                          row one __ballot and one __popcll per wave, both 32-bit halves of every compared word
+//   k_poll_count_timed<L, C>  the same walk with the replicas part under the TIME rule (jg_isr_clock.h; the part is implied,
+//                          and wanted alone it is k_isrc_count's): the mask byte joins the loads of a pass, the word is
+//                          jg_isrc_word as it stands - the stamp gathers and, unless peeking, the stores of the clocks
+//                          behind its own conditions - and no lag policy is read: 89 bytes where all three are wanted and no
+//                          clock runs.  Its cnt[tile] / bsum[tile] are what k_isrc_write indexes
 //   k_scan_block_sums      (jg_sparse.h) one launch, one workgroup per wanted feed's bsum array
 //
-// Nothing here writes a column of the state machine or a shadow: the only stores are the scratch.
+// Nothing here writes a column of the state machine or a shadow: the only stores are the scratch and, in the timed pass of
+// a call that does not peek, the clocks - a slot is one lane's from load to store, no atomics.
 #pragma once
 #include "jg_commits.h"
 #include "jg_isr.h"
+#include "jg_isr_clock.h"
 #include "jg_watch.h"
 
 static_assert(JG_WATCH_TILE == JG_ISR_TILE && JG_ISR_TILE == JG_CMT_TILE, "the three write passes index one tiling");
 #define JG_POLL_ROWS JG_CMT_ROWS
 #define JG_POLL_TILE JG_CMT_TILE
+static_assert(JG_ISR_TILE == JG_POLL_TILE, "k_isrc_write (jg_isr_clock.h) indexes the tiling of the timed pass");
 // rows of a tile whose loads are in flight together: 22 dwords a row where all three feeds are wanted
 #define JG_POLL_FLIGHT 4u
 static_assert(JG_POLL_ROWS % JG_POLL_FLIGHT == 0, "a tile is whole passes");
@@ -35,17 +43,20 @@ struct JgPollArgs {
   JgWatchArgs lw;   // the arguments of the wanted feeds' own write passes: g0 and n are the same in all of them
   JgIsrArgs ir;
   JgCommitArgs cm;
+  JgIsrClockArgs ic;  // the replicas part under the time rule (k_poll_count_timed, k_isrc_write): in place of ir
 };
 
 // rows k0 .. k0 + JG_POLL_FLIGHT - 1 of a tile: c[x] += the slots of feed x (leaders, replicas, commits) that differ from
-// its shadow, wave-uniform; bc / commits / appends: the commit backlog as k_commit_count keeps it
-template <bool L, bool I, bool C>
+// its shadow, wave-uniform; bc / commits / appends: the commit backlog as k_commit_count keeps it.  T: the replicas part is
+// under the time rule - leave32 is then caught_lag's 32-bit clamp, and unless a.ic.peek the clocks of the rows advance
+template <bool L, bool I, bool C, bool T = false>
 __device__ __forceinline__ void jg_poll_rows(const JgDev& d, const JgPollArgs& a, uint32_t g0, uint32_t n, uint32_t tile, uint32_t k0,
                                              uint32_t leave32, uint32_t join32, uint32_t lane, uint32_t* c, uint32_t* bc, uint64_t& commits,
                                              uint64_t& appends) {
+  static_assert(I || !T, "the time rule is the replicas part's");
   const uint32_t t0 = tile * JG_POLL_TILE + k0 * JG_BLOCK + threadIdx.x;
   const uint32_t R = d.R;
-  uint32_t f[JG_POLL_FLIGHT], ish[JG_POLL_FLIGHT];
+  uint32_t f[JG_POLL_FLIGHT], ish[JG_POLL_FLIGHT], mk[JG_POLL_FLIGHT];
   uint64_t term[JG_POLL_FLIGHT], w[JG_POLL_FLIGHT], head[JG_POLL_FLIGHT], col[JG_POLL_FLIGHT];
   uint4 cold[JG_POLL_FLIGHT], lsh[JG_POLL_FLIGHT], csh[JG_POLL_FLIGHT];
 #pragma unroll
@@ -60,7 +71,8 @@ __device__ __forceinline__ void jg_poll_rows(const JgDev& d, const JgPollArgs& a
       lsh[k] = in ? a.lw.shadow[g] : make_uint4(0, 0, 0, 0);
     }
     if (I || C) w[k] = in ? d.mlag[g] : 0ull;
-    if (I) ish[k] = in ? a.ir.shadow[g] : 0u;
+    if (I) ish[k] = in ? (T ? a.ic.shadow : a.ir.shadow)[g] : 0u;
+    if (T) mk[k] = in ? (uint32_t)a.ic.mask[g] & ((1u << R) - 1u) : 0u;  // (no bit at or above R: no stamp column there)
     if (C) {
       head[k] = in ? d.head[g] : 0ull;
       col[k] = in ? d.commit[g] : 0ull;
@@ -74,6 +86,7 @@ __device__ __forceinline__ void jg_poll_rows(const JgDev& d, const JgPollArgs& a
     if (L) asm volatile("" ::"v"(term[k]), "v"(cold[k].y), "v"(lsh[k].x), "v"(lsh[k].z));
     if (I || C) asm volatile("" ::"v"(w[k]));
     if (I) asm volatile("" ::"v"(ish[k]));
+    if (T) asm volatile("" ::"v"(mk[k]));
     if (C) asm volatile("" ::"v"(head[k]), "v"(col[k]), "v"(csh[k].x), "v"(csh[k].z));
   }
 #pragma unroll
@@ -86,8 +99,12 @@ __device__ __forceinline__ void jg_poll_rows(const JgDev& d, const JgPollArgs& a
                            lsh[k].w != (v.meta ^ JG_WATCH_VACANT_META);
       c[0] += __popcll(__ballot(in && differs));
     }
-    if (I) {  // jg_isr_ballots
+    if (I && !T) {  // jg_isr_ballots
       const uint32_t v = in ? jg_isr_word(d, a.ir.leave_lag, a.ir.join_lag, leave32, join32, g0 + i, f[k], w[k], ish[k]) : 0u;
+      c[1] += __popcll(__ballot(in && v != ish[k]));
+    }
+    if (T) {  // jg_isrc_ballots: a lane beyond n stores no clock either
+      const uint32_t v = in ? jg_isrc_word(d, a.ic, leave32, join32, g0 + i, f[k], w[k], ish[k], mk[k], !a.ic.peek) : 0u;
       c[1] += __popcll(__ballot(in && v != ish[k]));
     }
     if (C) {  // jg_commit_ballots, and the backlog of k_commit_count
@@ -141,6 +158,57 @@ __global__ __launch_bounds__(JG_BLOCK) void k_poll_count(JgDev d, JgPollArgs a) 
       for (uint32_t y = 0; y < JG_BLOCK / 64; y++) t += wave_n[x][y];
       if (L && x == 0) a.lw.cnt[tile] = t, a.lw.bsum[tile] = t;
       if (I && x == 1) a.ir.cnt[tile] = t, a.ir.bsum[tile] = t;
+      if (C && x == 2) a.cm.cnt[tile] = t, a.cm.bsum[tile] = t;
+    }
+    __syncthreads();  // (wave_n is the next tile's too)
+  }
+  if (!C || !a.cm.backlog) return;
+  commits = jg_wave_sum64(commits);
+  appends = jg_wave_sum64(appends);
+  if (lane == 0) {
+#pragma unroll
+    for (uint32_t x = 0; x < 4; x++) wave_b[wave][x] = bc[x];
+    wave_b[wave][4] = commits;
+    wave_b[wave][5] = appends;
+  }
+  __syncthreads();
+  if (threadIdx.x < JG_CMT_WORDS) {
+    uint64_t t = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < JG_BLOCK / 64; x++) t += wave_b[x][threadIdx.x];
+    a.cm.part[(size_t)blockIdx.x * JG_CMT_WORDS + threadIdx.x] = t;
+  }
+}
+
+// k_poll_count's walk with the replicas part under the time rule: L / C the other feeds wanted (one of them at least)
+template <bool L, bool C>
+__global__ __launch_bounds__(JG_BLOCK) void k_poll_count_timed(JgDev d, JgPollArgs a) {
+  static_assert(L || C, "a timed replicas part wanted alone is k_isrc_count's");
+  __shared__ uint32_t wave_n[3][JG_BLOCK / 64];
+  __shared__ uint64_t wave_b[JG_BLOCK / 64][JG_CMT_WORDS];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t g0 = a.ic.g0, n = a.ic.n;
+  const uint32_t caught32 = a.ic.caught_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.ic.caught_lag;
+  const uint32_t join32 = a.ic.join_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.ic.join_lag;
+  uint32_t bc[4] = {0u, 0u, 0u, 0u};  // changed, committed, appended, rewound: wave-uniform
+  uint64_t commits = 0, appends = 0;  // per lane
+  for (uint32_t tile = blockIdx.x; tile < a.tiles; tile += a.parts) {  // (uniform over the workgroup)
+    uint32_t c[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t k0 = 0; k0 < JG_POLL_ROWS; k0 += JG_POLL_FLIGHT)
+      jg_poll_rows<L, true, C, true>(d, a, g0, n, tile, k0, caught32, join32, lane, c, bc, commits, appends);
+    if (lane == 0) {
+#pragma unroll
+      for (uint32_t x = 0; x < 3; x++) wave_n[x][wave] = c[x];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {  // thread x: feed x's count of the tile
+      const uint32_t x = threadIdx.x;
+      uint32_t t = 0;
+#pragma unroll
+      for (uint32_t y = 0; y < JG_BLOCK / 64; y++) t += wave_n[x][y];
+      if (L && x == 0) a.lw.cnt[tile] = t, a.lw.bsum[tile] = t;
+      if (x == 1) a.ic.cnt[tile] = t, a.ic.bsum[tile] = t;
       if (C && x == 2) a.cm.cnt[tile] = t, a.cm.bsum[tile] = t;
     }
     __syncthreads();  // (wave_n is the next tile's too)

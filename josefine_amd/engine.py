@@ -808,6 +808,9 @@ class BatchedRaft(_Hosting):
         device pass, one synchronisation - each exactly as its separate method answers it.  A feed argument is None (not
         asked: its shadow is not touched), True, or that feed's options as a dict or a tuple in this order:
         leaders (limit, peek); replicas (leave_lag, join_lag, limit, peek); commits (limit, peek, commits_only, backlog).
+        A `replicas` dict that names `now_ms` asks for the TIME rule (watch_replicas_timed; ABI v20): its keys are now_ms,
+        max_behind_ms, caught_lag = 0, join_lag = 0, limit, peek - unless `peek`, the clocks of every slot of the range
+        advance to now_ms, whatever `limit` is; naming leave_lag beside them is a TypeError.
         `census`: jg_engine_census too; `repl_census`: the lag limit of jg_engine_replication_census, or None.  Returns a
         dict keyed by the parts asked for: "leaders" / "replicas" (rows, total), "commits" (rows, total) or with backlog
         (rows, total, backlog), "census" / "repl_census" the dicts of census() / replication_census()."""
@@ -839,10 +842,18 @@ class BatchedRaft(_Hosting):
             p.leaders_cap, keep["leaders"] = rows_of(o["limit"], capi.LEADER_ROW_DTYPE)
             p.leaders = keep["leaders"].ctypes.data
         if replicas is not None:
-            o = options(replicas, ("leave_lag", "join_lag", "limit", "peek"), dict(join_lag=None, limit=None, peek=False))
+            if isinstance(replicas, dict) and "now_ms" in replicas:  # the time rule
+                if "leave_lag" in replicas:
+                    raise TypeError("poll: replicas names now_ms (the time rule) and leave_lag (the lag rule)")
+                o = options(replicas, ("now_ms", "max_behind_ms", "caught_lag", "join_lag", "limit", "peek"),
+                            dict(caught_lag=0, join_lag=0, limit=None, peek=False))
+                keep["clock"] = capi.IsrClock(int(o["now_ms"]), int(o["max_behind_ms"]), int(o["caught_lag"]), int(o["join_lag"]))
+                p.clock = C.pointer(keep["clock"])
+            else:
+                o = options(replicas, ("leave_lag", "join_lag", "limit", "peek"), dict(join_lag=None, limit=None, peek=False))
+                p.policy = capi.IsrPolicy(int(o["leave_lag"]), int(o["leave_lag"] if o["join_lag"] is None else o["join_lag"]))
             p.want |= capi.POLL_REPLICAS
             p.replica_flags = capi.WATCH_PEEK if o["peek"] else 0
-            p.policy = capi.IsrPolicy(int(o["leave_lag"]), int(o["leave_lag"] if o["join_lag"] is None else o["join_lag"]))
             p.replicas_cap, keep["replicas"] = rows_of(o["limit"], capi.ISR_ROW_DTYPE)
             p.replicas = keep["replicas"].ctypes.data
         backlog = False

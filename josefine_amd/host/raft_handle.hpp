@@ -391,7 +391,9 @@ class BatchedRaft {
   // watch_leaders, watch_replicas, watch_commits, census and replication_census over [g0, g0 + n) in ONE call - one settle,
   // one device pass over the slots, one synchronisation - each exactly as its own call answers it, the shadows shared with
   // them.  A part not named is neither computed nor advanced.  Read the answers in the order leaders, replicas, commits: a
-  // role change is known before the ranges of the commit rows are applied.
+  // role change is known before the ranges of the commit rows are applied.  With `timed` (ABI v20) the replicas part is
+  // watch_replicas_timed's under `clock` - `policy` is not read - and unless replicas_peek the clocks of every slot of the
+  // range advance to clock.now_ms, whatever replicas_limit is.
   struct PollRequest {
     uint32_t want = JG_POLL_LEADERS | JG_POLL_REPLICAS | JG_POLL_COMMITS;
     uint32_t g0 = 0, n = UINT32_MAX;
@@ -399,6 +401,8 @@ class BatchedRaft {
     bool leaders_peek = false, replicas_peek = false, commits_peek = false;
     bool commits_only = false;
     jg_isr_policy policy{0, 0};    // JG_POLL_REPLICAS
+    bool timed = false;             // JG_POLL_REPLICAS under the time rule of `clock`
+    jg_isr_clock clock{0, 0, 0, 0};
     uint64_t census_lag_limit = 0;  // JG_POLL_REPL_CENSUS
   };
   struct PollResult {
@@ -418,6 +422,7 @@ class BatchedRaft {
     p.replica_flags = q.replicas_peek ? (uint32_t)JG_WATCH_PEEK : 0u;
     p.commit_flags = (q.commits_peek ? (uint32_t)JG_WATCH_PEEK : 0u) | (q.commits_only ? (uint32_t)JG_WATCH_COMMITS_ONLY : 0u);
     p.policy = q.policy, p.census_lag_limit = q.census_lag_limit;
+    p.clock = q.timed ? &q.clock : nullptr;
     if (q.want & JG_POLL_LEADERS) r.leaders.resize(std::min<size_t>(q.leaders_limit, p.n));
     if (q.want & JG_POLL_REPLICAS) r.replicas.resize(std::min<size_t>(q.replicas_limit, p.n));
     if (q.want & JG_POLL_COMMITS) r.commits.resize(std::min<size_t>(q.commits_limit, p.n));
