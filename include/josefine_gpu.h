@@ -1298,12 +1298,23 @@ int jg_read_state(jg_engine* e, int field, uint32_t replica, void* out, uint32_t
 
 /* Counters since creation: [0] commands applied, [1] quorum decisions
  * (Leader::commit evaluations + election_status evaluations),
- * [2] group-steps of the dense path, [3] kernel launches. */
+ * [2] group-steps of the dense path, [3] kernel launches (a dense ack tick counts once, also where the engine
+ * issues it as two half-grids - see "device-resident helpers" below -, plus one for the general-path kernel
+ * where that is scheduled behind it). */
 int jg_get_counters(jg_engine* e, uint64_t out[4]);
 
 /* ---- device-resident helpers for benchmarks ---------------------------------
  * The engine owns its stream; these let a caller keep inputs in HBM and time
- * the stream with HIP events without linking the HIP runtime itself. */
+ * the stream with HIP events without linking the HIP runtime itself.
+ * Streams: between 1 M and 4 M groups (JG_DENSE_SPLIT_MIN in the environment at jg_engine_create: the lower end,
+ * then with no upper end; 0: never) jg_step_dense_acks_device issues the tick as two launches, the second half of
+ * the groups on a second stream the engine owns, and consecutive ticks of the two halves overlap.  Nothing of this
+ * is visible through the API: every other call - steps, reads, drains, feeds, jg_sync, jg_stream_wait,
+ * jg_timer_start / jg_timer_stop, the jg_device_* helpers - is ordered behind both halves and ahead of the next
+ * tick's, and the engine is "idle" only when both streams are.  As before, the ack block of a device-pointer tick
+ * must be complete when the call is made and must stay untouched until a later call on the engine has
+ * synchronised (or been ordered behind the tick: anything issued through the engine is); a caller's own work on
+ * another stream is neither waited for nor delayed. */
 int jg_device_alloc(jg_engine* e, size_t bytes, void** dev_ptr);
 int jg_device_free(jg_engine* e, void* dev_ptr);
 int jg_device_upload(jg_engine* e, void* dev_dst, const void* host_src, size_t bytes);

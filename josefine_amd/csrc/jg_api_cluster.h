@@ -129,6 +129,8 @@ int jg_dense_cluster_create(jg_engine* const* nodes, uint32_t n_nodes, uint32_t 
     return rc;
   }
   c->own_stream.assign(n_nodes, nullptr);
+  // (a node's columns are read and written through the lead node's handle from here on: its own ticks stay whole)
+  for (uint32_t r = 0; r < n_nodes; r++) nodes[r]->clustered = true;
   for (uint32_t r = 0; r < n_nodes; r++) {
     jg_engine* e = nodes[r];
     if (e == L || e->device != L->device) continue;
@@ -146,6 +148,7 @@ int jg_dense_cluster_create(jg_engine* const* nodes, uint32_t n_nodes, uint32_t 
 
 void jg_dense_cluster_destroy(jg_dense_cluster* c) {
   if (!c) return;
+  for (jg_engine* e : c->nodes) e->clustered = false;
   for (size_t r = 0; r < c->own_stream.size(); r++)
     if (c->own_stream[r]) {
       (void)hipStreamSynchronize(c->nodes[r]->stream);

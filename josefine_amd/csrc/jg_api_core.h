@@ -180,11 +180,51 @@ struct JgSeg {
 
 }  // namespace
 
+// the sizes at which the dense ack tick is split when JG_DENSE_SPLIT_MIN is not set: the smallest and the largest measured
+// size at which it wins beyond the run-to-run spread (jg_engine_create; profiles/r07/ab_dense_two_queues.txt)
+#define JG_DENSE_SPLIT_MIN_DEFAULT 1000000u
+#define JG_DENSE_SPLIT_MAX_DEFAULT 4000000u
+
+// The engine's stream as every entry point uses it.  A dense tick of the headline shape is cut into two launches, the
+// second on a stream of its own (launch_dense_split below), and whatever touches the engine's stream afterwards has to find both
+// halves ordered before it.  So nothing reads the handle without passing here: the conversion first makes the engine's
+// stream wait for an outstanding second half (jg_stream_join), notes that the stream has been used - the next split
+// tick's second half then waits for that work - and only then yields the handle.  Launches, copies, event records,
+// synchronisations and comparisons all go through it unedited; only the split itself and the stream's creation and
+// destruction name `raw`.
+struct jg_engine;
+hipStream_t jg_stream_join(jg_engine* e);
+struct JgStream {
+  hipStream_t raw = nullptr;
+  jg_engine* eng = nullptr;
+  operator hipStream_t() const { return eng ? jg_stream_join(eng) : raw; }
+  // engines that share a stream (a jg_dense_cluster's nodes): the handle changes hands, every engine keeps joining its own split
+  JgStream& operator=(const JgStream& o) {
+    raw = o.raw;
+    return *this;
+  }
+  JgStream& operator=(hipStream_t s) {
+    raw = s;
+    return *this;
+  }
+};
+
 struct jg_engine {
+  jg_engine() { stream.eng = this; }
+  jg_engine(const jg_engine&) = delete;
+  jg_engine& operator=(const jg_engine&) = delete;
   jg_config cfg;
   JgDev dev;
   int device = 0;
-  hipStream_t stream = nullptr;
+  JgStream stream;
+  // the split dense tick: groups [0, split_cut) on `stream`, [split_cut, G) on stream_b, which free-run from tick to tick
+  hipStream_t stream_b = nullptr;
+  hipEvent_t ev_b_done = nullptr, ev_main_done = nullptr;  // (no timing) behind the second half / behind the engine's stream
+  uint32_t split_min = 0;        // JG_DENSE_SPLIT_MIN: the fewest groups a tick is split at (0: never)
+  uint32_t split_cut = 0;        // ceil(G / 2) rounded up to a workgroup; 0: this engine never splits
+  bool split_pending = false;    // stream_b holds a half-tick the engine's stream has not waited for
+  bool main_used = true;         // the engine's stream was handed out since the last split tick
+  bool clustered = false;        // a node of a jg_dense_cluster: its state is also worked on through other engines' handles
   hipStream_t own_stream = nullptr;  // non-null while a jg_dense_cluster has this node on its lead node's stream: the stream to destroy
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_stage = nullptr, ev_order = nullptr;
   std::vector<void*> allocs;
@@ -347,6 +387,8 @@ struct jg_engine {
   bool flag_check_pending = false;
   uint64_t irr_gen = 0;  // bumped by every step that sets flag_check_pending (a pipelined status snapshot settles the flag only if nothing did since)
   bool slow_scheduled_ever = false;  // some dense launch had k_dense_slow behind it
+  // n_launch: kernel launches as the work is defined - a dense tick is ONE, split into two half-grids or not (+ 1 for the
+  // slow kernel where it is scheduled behind it)
   uint64_t n_cmds = 0, n_dense = 0, n_launch = 0;
   // set while a jg_dense_cluster round is being captured into a hipGraph: the node kernels then
   // take logical time and step number from this device-resident clock instead of their arguments
@@ -447,6 +489,17 @@ struct jg_engine {
   uint32_t kt_every = 1, kt_seen = 0;  // every kt_every-th dense launch is timed (two event records cost the stream a few microseconds)
 };
 
+// (errors of the two calls surface at the call the handle goes to: the same sticky error)
+inline hipStream_t jg_stream_join(jg_engine* e) {
+  if (e->split_pending) {
+    e->split_pending = false;
+    (void)hipEventRecord(e->ev_b_done, e->stream_b);
+    (void)hipStreamWaitEvent(e->stream.raw, e->ev_b_done, 0);
+  }
+  e->main_used = true;
+  return e->stream.raw;
+}
+
 namespace {
 
 template <typename T>
@@ -475,6 +528,32 @@ inline uint32_t grid_for(size_t n, uint32_t cap) {
 //   ClientRequest       : forward / queue; Notify + Apply range
 inline uint32_t msg_bound(uint32_t R) { return R + 1 < 2 ? 2 : R + 1; }
 inline uint32_t fsm_bound() { return 2; }
+
+// ---- the headline tick as two launches on two streams ----------------------------------------------------------------------
+// Groups are independent: tick t + 1 of a group needs tick t of that group only.  Two fixed ranges, each ticking on a
+// stream of its own, free-run: while one range's kernel ramps up or drains - the part of a 1 M x 5 launch that does not
+// fill the memory system - the other range's kernel has the machine.  Only the plain ack tick with no slow kernel behind it
+// (launch_dense's last case) on an engine of its own; in steady ticking no event is recorded: the engine's stream is
+// joined when something else asks for it (JgStream), and the second half waits for the engine's stream only if that
+// happened since the last split tick.
+inline bool dense_splits(const jg_engine* e) {
+  return e->split_cut && !e->kt_on && !e->parent && !e->clustered;
+}
+template <int R>
+void launch_dense_split(jg_engine* e, const uint64_t* acks) {
+  const uint32_t G = e->dev.G, cut = e->split_cut;
+  const uint32_t grid_a = cut / JG_BLOCK, grid_b = (G - cut + JG_BLOCK - 1) / JG_BLOCK;  // (grid_a + grid_b = dense_grid <= count_slots)
+  if (e->main_used) {  // (which also joined: the second half's stream is ordered behind everything before this tick)
+    (void)hipEventRecord(e->ev_main_done, e->stream.raw);
+    (void)hipStreamWaitEvent(e->stream_b, e->ev_main_done, 0);
+    e->main_used = false;
+  }
+  hipLaunchKernelGGL((k_leader_tick_dense<R, false>), dim3(grid_a), dim3(JG_BLOCK), 0, e->stream.raw,
+                     jg_dense_hot_range(e->dev, 0, cut, 0), (const JgDev*)e->d_dev, acks, e->seq, e->uniform_self);
+  hipLaunchKernelGGL((k_leader_tick_dense<R, false>), dim3(grid_b), dim3(JG_BLOCK), 0, e->stream_b,
+                     jg_dense_hot_range(e->dev, cut, G, grid_a), (const JgDev*)e->d_dev, acks, e->seq, e->uniform_self);
+  e->split_pending = true;
+}
 
 template <int R>
 void launch_dense(jg_engine* e, const uint64_t* acks, uint32_t n_ticks, const JgLeaderNode* nd) {
@@ -506,6 +585,8 @@ void launch_dense(jg_engine* e, const uint64_t* acks, uint32_t n_ticks, const Jg
   else if (e->maybe_irregular)  // k_dense_slow is scheduled behind it: the kernel hands its general path to that one too
     hipLaunchKernelGGL((k_leader_tick_dense<R, true>), dim3(e->dense_grid), dim3(JG_BLOCK), 0, e->stream,
                        jg_dense_hot_of(e->dev), (const JgDev*)e->d_dev, acks, e->seq, e->uniform_self);
+  else if (dense_splits(e))
+    launch_dense_split<R>(e, acks);
   else
     hipLaunchKernelGGL((k_leader_tick_dense<R, false>), dim3(e->dense_grid), dim3(JG_BLOCK), 0, e->stream,
                        jg_dense_hot_of(e->dev), (const JgDev*)e->d_dev, acks, e->seq, e->uniform_self);

@@ -39,8 +39,12 @@ int jg_engine_create(const jg_config* cfg, jg_engine** out) {
     jg_engine_destroy(e);
     return code;
   };
-  if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
+  if (hipStreamCreateWithFlags(&e->stream.raw, hipStreamNonBlocking) != hipSuccess ||
+      hipStreamCreateWithFlags(&e->stream_b, hipStreamNonBlocking) != hipSuccess)
     return bail(fail(JG_EDEVICE, "hipStreamCreate failed"));
+  if (hipEventCreateWithFlags(&e->ev_b_done, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&e->ev_main_done, hipEventDisableTiming) != hipSuccess)
+    return bail(fail(JG_EDEVICE, "hipEventCreate failed"));
   if (hipEventCreate(&e->ev0) != hipSuccess || hipEventCreate(&e->ev1) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_stage, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_order, hipEventDisableTiming) != hipSuccess)
@@ -66,6 +70,17 @@ int jg_engine_create(const jg_config* cfg, jg_engine** out) {
   if (cap < 1) cap = 1;
   e->dense_grid = grid_for(G, cap);
   e->count_slots = std::max<uint32_t>(e->dense_grid, 4096);
+  {  // the split dense tick (launch_dense_split): from JG_DENSE_SPLIT_MIN groups on (0: never), where the grid is one pass
+     // and both halves are non-empty.  Unset: the measured window (profiles/r07/ab_dense_two_queues.txt) - at 1 M and 4 M
+     // groups x 5 the split wins by 14 % and 6 %, at 250 k it loses (two launches per tick are launch-bound there), at 500 k
+     // the gain is within three times the spread, at 16 M there is none.  A value from the environment has no upper end.
+    const char* env_split = std::getenv("JG_DENSE_SPLIT_MIN");
+    e->split_min = env_split ? (uint32_t)std::strtoul(env_split, nullptr, 10) : JG_DENSE_SPLIT_MIN_DEFAULT;
+    const size_t split_max = env_split ? ~size_t(0) : (size_t)JG_DENSE_SPLIT_MAX_DEFAULT;
+    const size_t cut = (((G + 1) / 2 + JG_BLOCK - 1) / JG_BLOCK) * JG_BLOCK;
+    if (e->split_min && G >= e->split_min && G <= split_max && cut < G && (G + JG_BLOCK - 1) / JG_BLOCK == e->dense_grid)
+      e->split_cut = (uint32_t)cut;
+  }
 #define A(ptr, n) \
   if ((rc = dev_alloc(e, &ptr, (n))) != JG_OK) return bail(rc)
   A(d.term, G);
@@ -152,7 +167,8 @@ void jg_engine_destroy(jg_engine* e) {
     delete e->drain_thread;
     e->drain_thread = nullptr;
   }
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
+  if (e->stream.raw) (void)hipStreamSynchronize(e->stream);  // (joins an outstanding half-tick first: nothing is freed under it)
+  if (e->stream_b) (void)hipStreamSynchronize(e->stream_b);
   if (e->copy_stream) (void)hipStreamSynchronize(e->copy_stream);
   e->arenas[0].destroy();
   e->arenas[1].destroy();
@@ -217,7 +233,10 @@ void jg_engine_destroy(jg_engine* e) {
   // (an engine destroyed while still in a jg_dense_cluster - against the documented order - must not
   // destroy the lead node's stream it was lent: its own one is the one to release)
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
-  else if (e->stream) (void)hipStreamDestroy(e->stream);
+  else if (e->stream.raw) (void)hipStreamDestroy(e->stream.raw);
+  if (e->stream_b) (void)hipStreamDestroy(e->stream_b);
+  if (e->ev_b_done) (void)hipEventDestroy(e->ev_b_done);
+  if (e->ev_main_done) (void)hipEventDestroy(e->ev_main_done);
   delete e;
 }
 

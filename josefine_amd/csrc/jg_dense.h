@@ -51,9 +51,19 @@ struct JgDenseHot {
   uint32_t hb_timeout, cfg_flags;
   uint64_t* term;
   uint64_t* heartbeat_time;
+  // the groups this launch serves: [g_begin, g_end), g_begin a multiple of JG_BLOCK (a wave's 64 groups are one word of the
+  // deferral bitmap).  All of them, except where the host cuts a tick into two launches (jg_dense_hot_range)
+  uint32_t g_begin, g_end;
 };
 __host__ __device__ __forceinline__ JgDenseHot jg_dense_hot_of(const JgDev& d) {
-  return JgDenseHot{d.flags, d.mlag, d.head, d.blk_decisions, d.G, d.hb_timeout, d.cfg_flags, d.term, d.heartbeat_time};
+  return JgDenseHot{d.flags, d.mlag, d.head, d.blk_decisions, d.G, d.hb_timeout, d.cfg_flags, d.term, d.heartbeat_time, 0u, d.G};
+}
+// The same for the groups [begin, end) alone, launched with ceil((end - begin) / JG_BLOCK) workgroups of their own:
+// `slot0` is the first of the launch's decision slots (blockIdx.x counts from 0 in every launch).
+__host__ __device__ __forceinline__ JgDenseHot jg_dense_hot_range(const JgDev& d, uint32_t begin, uint32_t end, uint32_t slot0) {
+  JgDenseHot h = jg_dense_hot_of(d);
+  h.blk_decisions += slot0, h.g_begin = begin, h.g_end = end;
+  return h;
 }
 
 
@@ -854,11 +864,11 @@ template <int R, bool UNIFORM, bool NODE, bool DEFER, bool FSM = false, bool ANY
 __device__ __forceinline__ JgDecCount jg_dense_tick_body(const JgDenseHot& h, const JgDev* dp,
                                                        const uint64_t* __restrict__ acks, uint32_t seq, uint32_t us,
                                                        const JgLeaderNode& nd, uint64_t (*sm)[JG_BLOCK]) {
-  const uint32_t G = h.G, stride = gridDim.x * JG_BLOCK;
+  const uint32_t end = h.g_end, stride = gridDim.x * JG_BLOCK;
   const bool emit = NODE && nd.o_beat != nullptr;
   JgDecCount dec;
-  uint32_t g = blockIdx.x * JG_BLOCK + threadIdx.x;
-  for (; g < G; g += stride) {
+  uint32_t g = h.g_begin + blockIdx.x * JG_BLOCK + threadIdx.x;
+  for (; g < end; g += stride) {
     if (FSM && nd.sparse_bits && jg_sparse_skip(nd.sparse_bits, nd.sparse_mode, g)) continue;
     if (ANY) {  // the flag word first: a wave that leads none of its 64 groups loads nothing else (a node leads G / R of them)
       const uint32_t f0 = h.flags[g];
