@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 20u /* v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 21u /* v21: jg_step_node_polled / jg_node_poll_view (a poll behind a kept node step: the feeds with two ticks in flight); v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -1126,6 +1126,61 @@ int jg_step_node(jg_engine* e, uint64_t now_ms, uint32_t flags);
  * until the next jg_step_node.  On a multi-device engine the columns are the shards' concatenated.
  * (JG_NODE_KEEP: the OLDEST step whose outbox has not been viewed - see there.) */
 int jg_node_outbox_view(jg_engine* e, jg_node_outbox* out);
+
+/* ---- a poll behind a kept node step: the feeds with two ticks in flight (ABI v21) --------------------
+ * jg_engine_poll and the separate feed calls are refused while kept node steps are outstanding: between
+ * two steps whose outputs are not due a synchronous answer has no place.  In a loop that always has a
+ * step outstanding (JG_NODE_ASYNC | JG_NODE_KEEP, two ticks in flight) that is every tick.  A POLLED step
+ * carries its poll with it: queued behind the step's own kernels, it sees the engine exactly as that step
+ * leaves it, travels home on the step's own trip and is handed out when that step's outbox is viewed.
+ * Nothing is synchronised that jg_step_node with JG_NODE_KEEP does not synchronise.  It defines no value
+ * of its own:
+ *
+ * CONTRACT.  Let S be the engine after step t is settled and before anything else touches it.  The answer
+ * viewed for step t is what jg_engine_poll with the same jg_poll leaves when called on S: every row byte,
+ * every total, the backlog and both censuses; and the three shadows and the replication clocks are
+ * afterwards what that call leaves - JG_WATCH_PEEK counts per feed as there, and under the time rule the
+ * clocks of every slot of the range advance to clock->now_ms whatever the cap, unless the replicas part
+ * peeks.  Consecutive polled steps are consecutive polls: what a small cap leaves pending at step t is
+ * pending at step t + 1.  A kept step without a poll leaves the feeds alone.  jg_engine_poll and the
+ * separate feed calls stay refused while kept steps are outstanding; once none is they may be mixed with
+ * polled steps on one engine - one set of shadows, one set of clocks.
+ *
+ * jg_step_node_polled is jg_step_node(e, now_ms, flags) with *request attached.  request == NULL is
+ * exactly jg_step_node.  Otherwise flags must contain JG_NODE_KEEP (and so JG_NODE_ASYNC) and `e` must not
+ * be a multi-device parent (JG_NODE_KEEP is per shard already).  *request and, if JG_POLL_REPLICAS is
+ * wanted and clock != NULL, *request->clock are copied at entry.  READ are the input fields: want, g0, n,
+ * the three flag words, policy, census_lag_limit, clock and the three *_cap fields.  The output pointers
+ * are never written through: backlog != NULL only says "the backlog is wanted", the row and census
+ * pointers are ignored.  Every argument is checked by jg_engine_poll's own rules before anything of the
+ * step is queued: a refused call (JG_EINVAL) steps nothing and leaves the submitted rows queued.
+ *
+ * jg_node_poll_view answers for the kept step whose outbox jg_node_outbox_view finished last; JG_EINVAL if
+ * no kept step has been viewed yet.  want == 0: that step carried no poll (JG_OK, everything else 0).  The
+ * rows live in the engine's pinned memory, one landing area per kept-step set, and stay valid as long as
+ * that view's outbox columns do: until the next node step claims the set.  Each feed's rows come home
+ * behind the step, the copy sized from the polled step finished last; what is missing is fetched when the
+ * step is viewed.
+ *
+ * A step whose rows took the general path is completed by a catch-up pass when it is settled.  The poll
+ * queued behind such a step's first pass finds that out on the device (the step's general-row count) and
+ * writes neither shadow nor clock; the same request is queued once more behind the catch-up pass, and
+ * `state` says so: JG_NODE_POLL_REDONE, informational - the answer is S's either way. */
+enum { JG_NODE_POLL_REDONE = 1u };    /* jg_node_poll.state */
+typedef struct jg_node_poll {
+  uint32_t want, state;               /* the request's want (0: the step carried no poll); JG_NODE_POLL_*   */
+  const jg_leader_row* leaders;       /* [leaders_n], ascending; _n = min(cap, total)                       */
+  size_t leaders_n, leaders_total;
+  const jg_isr_row* replicas;
+  size_t replicas_n, replicas_total;
+  const jg_commit_row* commits;
+  size_t commits_n, commits_total;
+  jg_commit_backlog backlog;          /* zero unless wanted                                                 */
+  jg_census census;
+  jg_repl_census repl_census;
+} jg_node_poll;
+int jg_step_node_polled(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_poll* request);
+int jg_node_poll_view(jg_engine* e, jg_node_poll* out);
 
 /* ---- a closed loop of dense node ticks ------------------------------------------------------------
  * All R nodes of every partition in ONE process (one engine per node, e.g. the three brokers of

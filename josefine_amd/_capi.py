@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -266,6 +266,18 @@ class Poll(C.Structure):
                 ("clock", C.POINTER(IsrClock))]
 
 
+NODE_POLL_REDONE = 1  # jg_node_poll.state
+
+
+class NodePoll(C.Structure):
+    """jg_node_poll."""
+    _fields_ = [("want", C.c_uint32), ("state", C.c_uint32),
+                ("leaders", C.c_void_p), ("leaders_n", C.c_size_t), ("leaders_total", C.c_size_t),
+                ("replicas", C.c_void_p), ("replicas_n", C.c_size_t), ("replicas_total", C.c_size_t),
+                ("commits", C.c_void_p), ("commits_n", C.c_size_t), ("commits_total", C.c_size_t),
+                ("backlog", CommitBacklog), ("census", Census), ("repl_census", ReplCensus)]
+
+
 # mailbox words (josefine_gpu.h: JG_ANSWER / JG_AE)
 MAILBOX_NONE = (1 << 56) - 1
 
@@ -402,6 +414,8 @@ class Api:
         "engine_watch_commits": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                            C.POINTER(CommitBacklog)]),
         "engine_poll": (C.c_int, [_P, C.POINTER(Poll)]),
+        "step_node_polled": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.POINTER(Poll)]),
+        "node_poll_view": (C.c_int, [_P, C.POINTER(NodePoll)]),
     }
     # only the oracle has these
     _ORACLE_PROTOS = {
@@ -450,5 +464,6 @@ HEADER_SYMBOLS = [
     "jg_engine_lookup_groups",
     "jg_engine_watch_commits",
     "jg_engine_poll",
+    "jg_step_node_polled", "jg_node_poll_view",
     "jg_engine_watch_replicas_timed",
 ]

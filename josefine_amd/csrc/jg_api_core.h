@@ -408,6 +408,19 @@ struct jg_engine {
   // What ONE node step leaves for the host.  A step owns a set until the next step begins - or, taken with JG_NODE_KEEP,
   // until its outbox has been viewed: two such steps may be outstanding (the event loop's two ticks in flight), each in one
   // of NodeStep::sets.
+  // the poll of a kept node step: jg_poll's input fields, and the step's own bookkeeping
+  struct NodePoll {
+    uint32_t want = 0, g0 = 0, n = 0;
+    bool peek[3] = {false, false, false};
+    bool commits_only = false, backlog = false, timed = false;
+    jg_isr_policy pol{};
+    jg_isr_clock clk{};
+    uint64_t lag_limit = 0;
+    size_t cap[3] = {0, 0, 0};
+    char* scratch = nullptr;           // the set's arena: counts, tile sums, rows, partial records, the header block
+    size_t copied[3] = {0, 0, 0};      // rows of each feed the step's own copy brought home
+    bool redone = false;               // queued once more, ungated, behind the catch-up pass (JG_NODE_POLL_REDONE)
+  };
   struct NodeOut {
     jg_leader_beat* h_beat = nullptr;  // pinned mirrors of the outbox columns
     uint64_t *h_ae = nullptr, *h_answer = nullptr, *h_hbc = nullptr, *h_aec = nullptr;
@@ -440,6 +453,11 @@ struct jg_engine {
     bool fsm_landed = false;           // l_fsm is to be handed to q_fsm by the next drain of that queue
     uint64_t irr_gen = 0;
     uint32_t seq_hi = 0;               // the engine's step number after the step
+    // -- jg_step_node_polled: the poll that travels with the step (jg_api_poll.h) ----------------------------------------
+    NodePoll poll;                     // the request as copied at entry (want == 0: the step carries none) and where its answer is
+    uint64_t* h_poll = nullptr;        // pinned: the scan jobs the device reads, then where the header block lands
+    PinnedQueue<char> l_poll[3];       // pinned: where each feed's rows land (bytes); the first poll.copied[x] rows came with the step
+    jg_node_poll poll_view{};          // what jg_node_poll_view hands out once the step's outbox has been viewed
   };
   struct NodeStep {
     // The two sets.  `newest` is the one the newest step took (a kept step takes the other one, a plain step the same one
@@ -449,6 +467,9 @@ struct jg_engine {
     NodeOut& cur() { return sets[newest]; }
     // the set a view shows: the OLDEST outstanding step's - with none outstanding the newest's, which was viewed last
     NodeOut& to_view() { return sets[kept_n == 2 ? newest ^ 1u : newest]; }
+    int poll_viewed = -1;              // the set whose kept step's outbox view finished last (jg_node_poll_view answers for it)
+    size_t poll_guess[3] = {0, 0, 0};  // the feed totals of the polled step finished last: what sizes the next step's row copies
+    bool poll_guess_known = false;
     bool ready = false;
     JgNodeCols cols{};
     uint64_t *h_in_answers = nullptr, *h_in_hbc = nullptr;  // pinned [R][G]: column inbound (jg_node_inbox_columns)

@@ -104,6 +104,9 @@ int node_keep_finish(jg_engine* e, jg_engine::NodeOut& o);
 int node_dense_halves(jg_engine* e, uint64_t now_ms, uint32_t flags, uint32_t col_mask, uint32_t sparse_mode, uint64_t* bytes_down);
 int node_general(jg_engine* e, const JgNodeRows& rows, size_t n, size_t nb, uint32_t n_sparse, uint64_t now_ms);
 int node_fsm_record(jg_engine* e, StepRec& rec, uint32_t flags);
+// (jg_api_poll.h) the poll that travels with a kept step: queued behind its kernels, collected when its outbox is viewed
+int node_poll_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate);
+int node_poll_finish(jg_engine* e, jg_engine::NodeOut& o);
 
 // node_step (or node_settle's catch-up pass) is running: its halves' own node_settle calls are not another caller's
 struct InStep {
@@ -412,7 +415,8 @@ int node_publish(jg_engine* e, const NodeRun& s, uint32_t seq0, NodeClaim& claim
   return JG_OK;
 }
 
-int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags) {
+// `poll`: the request of a polled step (jg_step_node_polled: checked, and a kept step's), or null
+int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::NodePoll* poll) {
   static const bool trace = std::getenv("JG_TRACE_NODE") != nullptr;
   jg_engine::NodeStep& nd = e->node;
   NodeRun s;
@@ -427,6 +431,8 @@ int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags) {
   NodeClaim claim(e, s.keep);  // (from here on nd.cur() is this step's set)
   jg_engine::NodeOut& o = nd.cur();
   o.keep = s.keep, o.pending.on = false;
+  if (nd.poll_viewed == (int)nd.newest) nd.poll_viewed = -1;  // (the answer viewed last lived in this set)
+  o.poll = poll ? *poll : jg_engine::NodePoll{};
   if (s.keep) {  // (the set starts empty: its last step's regions went with that step's arena)
     o.set = e->cur_set, o.arena = e->cur_arena, o.irr_gen = e->irr_gen;
     o.d_fsm_cnt = nullptr, o.d_fsm = o.d_stage = nullptr, o.d_bsum = nullptr;
@@ -444,7 +450,10 @@ int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags) {
   // except in an asynchronous step, whose halves leave those partitions to the catch-up pass (node_settle)
   e->seq = seq0 + 1;  // (the halves number themselves from the general path's number, whether or not it ran)
   if ((rc = node_dense_halves(e, now_ms, flags, s.col_mask, s.async && s.n ? 1u : 0u, &s.bytes_down))) return rc;
-  if ((rc = node_tail(e, s)) || (rc = node_publish(e, s, seq0, claim))) return rc;
+  if ((rc = node_tail(e, s))) return rc;
+  // the poll behind the step: gated by the step's own general-row count, final once the route pass has run (no rows: no gate)
+  if (o.poll.want && (rc = node_poll_tail(e, o, s.n ? nd.d_nsparse : nullptr))) return rc;
+  if ((rc = node_publish(e, s, seq0, claim))) return rc;
   if (trace)
     std::fprintf(stderr, "[jg node] %zu rows: uploads + classify + route issued in %.0f us, waited %.0f us (H2D %.1f MB), halves + fsm build + outbox copies issued in %.0f us\n",
                  s.n, s.T1 - s.T0, s.T2 - s.T1, s.bytes_up / 1e6, node_clk() - s.T2);
@@ -608,6 +617,10 @@ int node_settle(jg_engine* e) {
   if ((rc = node_dense_halves(e, pd.now_ms, pd.flags, pd.col_mask, 2u, &bytes_down))) return rc;
   if (o.keep) {  // the step's fsm rows once more, from the deltas the catch-up pass completed
     if ((rc = node_keep_tail(e, pd.flags))) return rc;
+    if (o.poll.want) {  // ... and its poll: the first pass saw the count and peeked - the same request, ungated, on the settled state
+      o.poll.redone = true;
+      if ((rc = node_poll_tail(e, o, nullptr))) return rc;
+    }
     HIPCHK(hipEventRecord(o.ev_out, nd.down));
   }
   for (StepRec& rec : e->recs)
@@ -708,6 +721,7 @@ int node_keep_finish(jg_engine* e, jg_engine::NodeOut& o) {
   o.l_fsm.n = total, o.fsm_landed = total != 0;
   if (e->track_segs) seg_add(e->seg_f, o.seq_hi, total);
   nd.fsm_guess = total, nd.fsm_guess_known = true;
+  if ((rc = node_poll_finish(e, o))) return rc;  // (the rows its own copy did not bring: out of the arena, before it starts over)
   // everything the step allocated has been read - d_stage just above was the last: its arena starts over, here and nowhere
   // else (records, if it had any, were drained above)
   e->arenas[o.arena].reset();
@@ -725,7 +739,7 @@ int jg_step_node(jg_engine* e, uint64_t now_ms, uint32_t flags) {
   if (e->router && (flags & (JG_NODE_COMMON_AE | JG_NODE_KEEP))) return fail(JG_EINVAL, "jg_step_node: JG_NODE_COMMON_AE and JG_NODE_KEEP are per shard (jg_get_shard)");
   if (e->router) return router_step_node(e, now_ms, flags);
   if (e->inflight.phase) return fail(JG_EINVAL, "a drain is in transfer: jg_drain_wait first");
-  return node_step(e, now_ms, flags);
+  return node_step(e, now_ms, flags, nullptr);
 }
 
 int jg_node_inbox_columns(jg_engine* e, uint32_t slot, uint64_t** answer, uint64_t** hb_commit) {

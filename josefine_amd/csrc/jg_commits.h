@@ -51,6 +51,7 @@ struct JgCommitArgs {
   uint64_t* sum;          // [JG_CMT_WORDS] the backlog
   uint4* out;             // [cap] rows of three 16-byte pieces (device)
   uint64_t cap;
+  const uint32_t* gate;  // null, or a device word: nonzero = behave as under peek (a polled node step whose rows took the general path)
 };
 
 __device__ __forceinline__ uint64_t jg_cmt_u64(uint32_t lo, uint32_t hi) { return (uint64_t)lo | (uint64_t)hi << 32; }
@@ -158,6 +159,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_commit_write(JgDev d, JgCommitArgs
   uint64_t commit[JG_CMT_ROWS], head[JG_CMT_ROWS], m[JG_CMT_ROWS];
   uint4 sh[JG_CMT_ROWS];
   jg_commit_ballots(d, a, blockIdx.x, f, commit, head, sh, m);
+  const uint32_t peek = jg_gated_peek(a.peek, a.gate);
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t t0 = blockIdx.x * JG_CMT_TILE + threadIdx.x;
   uint64_t term[JG_CMT_ROWS];
@@ -194,7 +196,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_commit_write(JgDev d, JgCommitArgs
       out[pos * 3 + 0] = jg_u32x4{a.add + g, role | state << 8 | fault << 16 | self << 24, lo(term[k]), hi(term[k])};
       out[pos * 3 + 1] = jg_u32x4{sh[k].x, sh[k].y, lo(commit[k]), hi(commit[k])};
       out[pos * 3 + 2] = jg_u32x4{sh[k].z, sh[k].w, lo(head[k]), hi(head[k])};
-      if (!a.peek) a.shadow[g] = make_uint4(lo(commit[k]), hi(commit[k]), lo(head[k]), hi(head[k]));
+      if (!peek) a.shadow[g] = make_uint4(lo(commit[k]), hi(commit[k]), lo(head[k]), hi(head[k]));
     }
     base += row;
   }

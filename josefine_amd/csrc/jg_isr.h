@@ -126,6 +126,7 @@ struct JgIsrArgs {
   uint64_t* bsum;    // [tiles] the same, then (k_scan_block_sums) their exclusive prefixes
   jg_isr_row* out;   // [cap] (device)
   uint64_t cap;
+  const uint32_t* gate;  // null, or a device word: nonzero = behave as under peek (a polled node step whose rows took the general path)
 };
 
 // a workgroup's rows: v[k] the view of slot t0 + k * JG_BLOCK as a shadow word, f[k] its flag word, w[k] its packed word,
@@ -181,6 +182,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_isr_write(JgDev d, JgIsrArgs a) {
   uint32_t v[JG_ISR_ROWS], f[JG_ISR_ROWS];
   uint64_t w[JG_ISR_ROWS], m[JG_ISR_ROWS];
   jg_isr_ballots(d, a, v, f, w, m);
+  const uint32_t peek = jg_gated_peek(a.peek, a.gate);
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t t0 = blockIdx.x * JG_ISR_TILE + threadIdx.x;
   uint64_t head[JG_ISR_ROWS];
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_isr_write(JgDev d, JgIsrArgs a) {
       out64[pos * 3 + 0] = (uint64_t)(a.add + g) | (uint64_t)(isr | replicate << 8 | state << 16 | self << 24) << 32;
       out64[pos * 3 + 1] = head[k];
       out64[pos * 3 + 2] = worst;
-      if (!a.peek) a.shadow[g] = v[k];
+      if (!peek) a.shadow[g] = v[k];
     }
     base += row;
   }

@@ -44,6 +44,7 @@ struct JgIsrClockArgs {
   uint64_t* bsum;      // [tiles] the same, then (k_scan_block_sums) their exclusive prefixes
   jg_isr_row* out;     // [cap] (device)
   uint64_t cap;
+  const uint32_t* gate;  // null, or a device word: nonzero = behave as under peek (a polled node step whose rows took the general path)
 };
 
 // The in-sync set of slot g under the time rule as the shadow holds it (isr | LEADS, 0 for a slot that does not lead) from
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_isrc_count(JgDev d, JgIsrClockArgs
   __shared__ uint32_t wave_n[JG_BLOCK / 64];
   uint32_t v[JG_ISR_ROWS], f[JG_ISR_ROWS];
   uint64_t w[JG_ISR_ROWS], m[JG_ISR_ROWS];
-  jg_isrc_ballots(d, a, !a.peek, v, f, w, m);
+  jg_isrc_ballots(d, a, !jg_gated_peek(a.peek, a.gate), v, f, w, m);
   uint32_t c = 0;
 #pragma unroll
   for (uint32_t k = 0; k < JG_ISR_ROWS; k++) c += __popcll(m[k]);
@@ -150,6 +151,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_isrc_write(JgDev d, JgIsrClockArgs
   uint32_t v[JG_ISR_ROWS], f[JG_ISR_ROWS];
   uint64_t w[JG_ISR_ROWS], m[JG_ISR_ROWS];
   jg_isrc_ballots(d, a, false, v, f, w, m);
+  const uint32_t peek = jg_gated_peek(a.peek, a.gate);
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t t0 = blockIdx.x * JG_ISR_TILE + threadIdx.x;
   uint64_t head[JG_ISR_ROWS];
@@ -189,7 +191,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_isrc_write(JgDev d, JgIsrClockArgs
       out64[pos * 3 + 0] = (uint64_t)(a.add + g) | (uint64_t)(isr | replicate << 8 | state << 16 | self << 24) << 32;
       out64[pos * 3 + 1] = head[k];
       out64[pos * 3 + 2] = worst;
-      if (!a.peek) a.shadow[g] = v[k];
+      if (!peek) a.shadow[g] = v[k];
     }
     base += row;
   }

@@ -256,7 +256,7 @@ int router_step(jg_engine* p, uint64_t now_ms) {
   return rc;
 }
 
-int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags);
+int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::NodePoll* poll);
 
 // jg_step_node on every shard (each one's rows were bucketed by jg_submit)
 int router_step_node(jg_engine* p, uint64_t now_ms, uint32_t flags) {
@@ -264,7 +264,7 @@ int router_step_node(jg_engine* p, uint64_t now_ms, uint32_t flags) {
   for (jg_engine* s : r.sh)
     if (s->inflight.phase) return fail(JG_EINVAL, "a drain is in transfer: jg_drain_wait first");
   router_align_seq(p);
-  const int rc = r.run([&](size_t d) { return node_step(r.sh[d], now_ms, flags); });
+  const int rc = r.run([&](size_t d) { return node_step(r.sh[d], now_ms, flags, nullptr); });
   router_after_step(p);
   p->node.cur().last_flags = flags;
   return rc;

@@ -20,6 +20,12 @@
 //                          behind its own conditions - and no lag policy is read: 89 bytes where all three are wanted and no
 //                          clock runs.  Its cnt[tile] / bsum[tile] are what k_isrc_write indexes
 //   k_scan_block_sums      (jg_sparse.h) one launch, one workgroup per wanted feed's bsum array
+//   k_poll_header          (at the end of this file) a polled node step's answer but the rows as one block: one copy home
+//
+// THE GATE (ABI v21).  The passes that act on a feed's peek - the write passes and the two count passes that advance clocks -
+// take an optional device word beside it (jg_gated_peek, jg_watch.h): null or zero, nothing changes; nonzero, the pass
+// behaves as under JG_WATCH_PEEK.  A poll queued behind a node step whose rows took the general path is gated by that step's
+// own general-row count: it writes no shadow and no clock, and is queued once more, ungated, behind the catch-up pass.
 //
 // Nothing here writes a column of the state machine or a shadow: the only stores are the scratch and, in the timed pass of
 // a call that does not peek, the clocks - a slot is one lane's from load to store, no atomics.
@@ -48,11 +54,12 @@ struct JgPollArgs {
 
 // rows k0 .. k0 + JG_POLL_FLIGHT - 1 of a tile: c[x] += the slots of feed x (leaders, replicas, commits) that differ from
 // its shadow, wave-uniform; bc / commits / appends: the commit backlog as k_commit_count keeps it.  T: the replicas part is
-// under the time rule - leave32 is then caught_lag's 32-bit clamp, and unless a.ic.peek the clocks of the rows advance
+// under the time rule - leave32 is then caught_lag's 32-bit clamp, and with `advance` (the call does not peek and its gate
+// is shut: uniform over the launch) the clocks of the rows advance
 template <bool L, bool I, bool C, bool T = false>
 __device__ __forceinline__ void jg_poll_rows(const JgDev& d, const JgPollArgs& a, uint32_t g0, uint32_t n, uint32_t tile, uint32_t k0,
-                                             uint32_t leave32, uint32_t join32, uint32_t lane, uint32_t* c, uint32_t* bc, uint64_t& commits,
-                                             uint64_t& appends) {
+                                             uint32_t leave32, uint32_t join32, uint32_t lane, bool advance, uint32_t* c, uint32_t* bc,
+                                             uint64_t& commits, uint64_t& appends) {
   static_assert(I || !T, "the time rule is the replicas part's");
   const uint32_t t0 = tile * JG_POLL_TILE + k0 * JG_BLOCK + threadIdx.x;
   const uint32_t R = d.R;
@@ -104,7 +111,7 @@ __device__ __forceinline__ void jg_poll_rows(const JgDev& d, const JgPollArgs& a
       c[1] += __popcll(__ballot(in && v != ish[k]));
     }
     if (T) {  // jg_isrc_ballots: a lane beyond n stores no clock either
-      const uint32_t v = in ? jg_isrc_word(d, a.ic, leave32, join32, g0 + i, f[k], w[k], ish[k], mk[k], !a.ic.peek) : 0u;
+      const uint32_t v = in ? jg_isrc_word(d, a.ic, leave32, join32, g0 + i, f[k], w[k], ish[k], mk[k], advance) : 0u;
       c[1] += __popcll(__ballot(in && v != ish[k]));
     }
     if (C) {  // jg_commit_ballots, and the backlog of k_commit_count
@@ -145,7 +152,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_poll_count(JgDev d, JgPollArgs a) 
     uint32_t c[3] = {0u, 0u, 0u};
 #pragma unroll
     for (uint32_t k0 = 0; k0 < JG_POLL_ROWS; k0 += JG_POLL_FLIGHT)
-      jg_poll_rows<L, I, C>(d, a, g0, n, tile, k0, leave32, join32, lane, c, bc, commits, appends);
+      jg_poll_rows<L, I, C>(d, a, g0, n, tile, k0, leave32, join32, lane, false, c, bc, commits, appends);
     if (lane == 0) {
 #pragma unroll
       for (uint32_t x = 0; x < 3; x++) wave_n[x][wave] = c[x];
@@ -190,13 +197,14 @@ __global__ __launch_bounds__(JG_BLOCK) void k_poll_count_timed(JgDev d, JgPollAr
   const uint32_t g0 = a.ic.g0, n = a.ic.n;
   const uint32_t caught32 = a.ic.caught_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.ic.caught_lag;
   const uint32_t join32 = a.ic.join_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.ic.join_lag;
+  const bool advance = !jg_gated_peek(a.ic.peek, a.ic.gate);  // (one scalar load per workgroup, outside the walk)
   uint32_t bc[4] = {0u, 0u, 0u, 0u};  // changed, committed, appended, rewound: wave-uniform
   uint64_t commits = 0, appends = 0;  // per lane
   for (uint32_t tile = blockIdx.x; tile < a.tiles; tile += a.parts) {  // (uniform over the workgroup)
     uint32_t c[3] = {0u, 0u, 0u};
 #pragma unroll
     for (uint32_t k0 = 0; k0 < JG_POLL_ROWS; k0 += JG_POLL_FLIGHT)
-      jg_poll_rows<L, true, C, true>(d, a, g0, n, tile, k0, caught32, join32, lane, c, bc, commits, appends);
+      jg_poll_rows<L, true, C, true>(d, a, g0, n, tile, k0, caught32, join32, lane, advance, c, bc, commits, appends);
     if (lane == 0) {
 #pragma unroll
       for (uint32_t x = 0; x < 3; x++) wave_n[x][wave] = c[x];
@@ -229,4 +237,48 @@ __global__ __launch_bounds__(JG_BLOCK) void k_poll_count_timed(JgDev d, JgPollAr
     for (uint32_t x = 0; x < JG_BLOCK / 64; x++) t += wave_b[x][threadIdx.x];
     a.cm.part[(size_t)blockIdx.x * JG_CMT_WORDS + threadIdx.x] = t;
   }
+}
+
+// ---- the header of a poll that travels with a node step (jg_step_node_polled) -------------------------------------------
+// Everything of the answer that is not a row, as ONE block of 8-byte words per kept-step set: one copy brings it home.
+#define JG_PH_TOTAL 0u                                  // [3] the slots of each feed that differ (leaders, replicas, commits)
+#define JG_PH_GIVEN 3u                                  // [3] min(cap, total): the rows delivered
+#define JG_PH_BACKLOG 6u                                // [JG_CMT_WORDS]
+#define JG_PH_CENSUS (JG_PH_BACKLOG + JG_CMT_WORDS)     // [JG_CENSUS_WORDS]
+#define JG_PH_REPL (JG_PH_CENSUS + JG_CENSUS_WORDS)     // [JG_RC_WORDS]
+#define JG_PH_GATE (JG_PH_REPL + JG_RC_WORDS)           // the gate's verdict: the step's general-path rows as this pass saw them
+#define JG_PH_WORDS (JG_PH_GATE + 1u)
+static_assert(JG_PH_WORDS <= JG_BLOCK, "one thread a word");
+
+struct JgPollHeaderArgs {
+  const uint64_t* total;    // what k_scan_block_sums left: one word per job
+  uint32_t job[3];          // feed x's job, or 0xffffffff: not wanted
+  uint32_t pad;
+  uint64_t cap[3];
+  const uint64_t* backlog;  // [JG_CMT_WORDS] or null
+  const uint64_t* census;   // [JG_CENSUS_WORDS] or null
+  const uint64_t* repl;     // [JG_RC_WORDS] or null
+  const uint32_t* gate;     // or null
+  uint64_t* out;            // [JG_PH_WORDS]
+};
+
+// one workgroup, one thread a word; a part that is not wanted is zeros
+__global__ __launch_bounds__(JG_BLOCK) void k_poll_header(JgPollHeaderArgs a) {
+  const uint32_t x = threadIdx.x;
+  if (x >= JG_PH_WORDS) return;
+  uint64_t v = 0;
+  if (x < JG_PH_BACKLOG) {
+    const uint32_t feed = x < JG_PH_GIVEN ? x : x - JG_PH_GIVEN;
+    const uint64_t t = a.job[feed] != 0xffffffffu ? a.total[a.job[feed]] : 0ull;
+    v = x < JG_PH_GIVEN ? t : (t < a.cap[feed] ? t : a.cap[feed]);
+  } else if (x < JG_PH_CENSUS) {
+    v = a.backlog ? a.backlog[x - JG_PH_BACKLOG] : 0ull;
+  } else if (x < JG_PH_REPL) {
+    v = a.census ? a.census[x - JG_PH_CENSUS] : 0ull;
+  } else if (x < JG_PH_GATE) {
+    v = a.repl ? a.repl[x - JG_PH_REPL] : 0ull;
+  } else {
+    v = a.gate ? *a.gate : 0u;
+  }
+  a.out[x] = v;
 }

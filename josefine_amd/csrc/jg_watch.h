@@ -66,6 +66,10 @@ __device__ __forceinline__ JgLeadView jg_lead_view(const JgDev& d, uint32_t f, u
   return v;
 }
 
+// the peek a pass acts on: the call's own, or the gate's verdict - ONE scalar load per workgroup (the pointer and the word are
+// uniform), taken behind the early return of a quiet workgroup, never inside the walk over the slots
+__device__ __forceinline__ uint32_t jg_gated_peek(uint32_t peek, const uint32_t* gate) { return peek | (gate ? *gate : 0u); }
+
 struct JgWatchArgs {
   uint32_t g0, n;    // shard-local slots [g0, g0 + n)
   uint32_t add;      // added to every group written (a shard's first global slot)
@@ -75,6 +79,7 @@ struct JgWatchArgs {
   uint64_t* bsum;    // [tiles] the same, then (k_scan_block_sums) their exclusive prefixes
   jg_leader_row* out;  // [cap] (device)
   uint64_t cap;
+  const uint32_t* gate;  // null, or a device word: nonzero = behave as under peek (a polled node step whose rows took the general path)
 };
 
 // a workgroup's rows: v[k] the view of slot t0 + k * JG_BLOCK, f[k] its flag word, bit l of m[k] = the slot of lane l of
@@ -132,6 +137,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_watch_write(JgDev d, JgWatchArgs a
   uint32_t f[JG_WATCH_ROWS];
   uint64_t m[JG_WATCH_ROWS];
   jg_watch_ballots(d, a, v, f, m);
+  const uint32_t peek = jg_gated_peek(a.peek, a.gate);
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   if (lane == 0) {
 #pragma unroll
@@ -157,7 +163,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_watch_write(JgDev d, JgWatchArgs a
       out64[pos * 3 + 0] = (uint64_t)(a.add + g) | (uint64_t)v[k].leader_id << 32;
       out64[pos * 3 + 1] = v[k].term;
       out64[pos * 3 + 2] = (uint64_t)(v[k].meta | self << 24);
-      if (!a.peek) a.shadow[g] = make_uint4((uint32_t)v[k].term, (uint32_t)(v[k].term >> 32), v[k].leader_id, v[k].meta ^ JG_WATCH_VACANT_META);
+      if (!peek) a.shadow[g] = make_uint4((uint32_t)v[k].term, (uint32_t)(v[k].term >> 32), v[k].leader_id, v[k].meta ^ JG_WATCH_VACANT_META);
     }
     base += row;
   }

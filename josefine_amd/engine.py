@@ -428,21 +428,67 @@ class BatchedRaft(_Hosting):
         return self.node_outbox()
 
     def step_node_begin(self, now_ms: int = 0, leader: bool = True, follower: bool = True, tick: bool = True, async_: bool = False,
-                        common_ae: bool = False, fsm_fused: bool = False, keep: bool = False) -> None:
+                        common_ae: bool = False, fsm_fused: bool = False, keep: bool = False, poll: Optional[dict] = None) -> None:
         """jg_step_node alone (the outbox: `node_outbox`).  keep (JG_NODE_KEEP, with async_): the step keeps its outputs
         until its outbox is viewed - a second such step may be begun before that; `node_outbox` then serves the OLDER
-        one and makes its rows the ones the next drains deliver."""
+        one and makes its rows the ones the next drains deliver.  poll (jg_step_node_polled, ABI v21; with keep): the
+        keyword arguments of `poll` as a dict - the poll travels with the step, sees the engine exactly as the step leaves
+        it and is handed out by `node_poll` once the step's outbox has been viewed."""
         self._flush_pending()
         flags = (capi.NODE_LEADER_HALF if leader else 0) | (capi.NODE_FOLLOWER_HALF if follower else 0) | \
                 (capi.NODE_TICK if tick else 0) | (capi.NODE_ASYNC if async_ else 0) | \
                 (capi.NODE_COMMON_AE if common_ae else 0) | (capi.NODE_FSM_FUSED if fsm_fused else 0) | \
                 (capi.NODE_KEEP if keep else 0)
-        self._check(self.api.step_node(self._h, int(now_ms), flags))
+        if poll is not None:
+            if not hasattr(self.api, "step_node_polled"):
+                raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}step_node_polled")
+            p, held, parts = self._poll_request(**poll)  # (`held`: what p points at, alive over the call)
+            self._check(self.api.step_node_polled(self._h, int(now_ms), flags, C.byref(p)))
+            del held
+        else:
+            self._check(self.api.step_node(self._h, int(now_ms), flags))
+        if keep:  # (what node_poll needs to know of the step and the view does not say: was the backlog asked for)
+            self.__dict__.setdefault("_kept_backlog", []).append(bool(poll is not None and parts["backlog"]))
+
+    def node_poll(self) -> dict:
+        """jg_node_poll_view: the answer of the poll that travelled with the kept step whose outbox `node_outbox` viewed
+        last, as host copies - the dict `poll` returns for the same arguments (every part the step's request named), plus
+        "redone": the step had general-path rows and the poll ran once more behind its catch-up pass (informational).  A
+        step that carried no poll: {"redone": False}."""
+        if not hasattr(self.api, "node_poll_view"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}node_poll_view")
+        v = capi.NodePoll()
+        self._check(self.api.node_poll_view(self._h, C.byref(v)))
+
+        def rows(p, k, dtype):
+            k = int(k)
+            if not k:
+                return np.zeros(0, dtype)
+            buf = (C.c_char * (k * np.dtype(dtype).itemsize)).from_address(p)
+            return np.frombuffer(buf, dtype=dtype).copy()
+
+        out = {}
+        if v.want & capi.POLL_LEADERS:
+            out["leaders"] = rows(v.leaders, v.leaders_n, capi.LEADER_ROW_DTYPE), int(v.leaders_total)
+        if v.want & capi.POLL_REPLICAS:
+            out["replicas"] = rows(v.replicas, v.replicas_n, capi.ISR_ROW_DTYPE), int(v.replicas_total)
+        if v.want & capi.POLL_COMMITS:
+            out["commits"] = rows(v.commits, v.commits_n, capi.COMMIT_ROW_DTYPE), int(v.commits_total)
+            if self.__dict__.get("_viewed_backlog", False):
+                out["commits"] += ({name: int(getattr(v.backlog, name)) for name, _ in capi.CommitBacklog._fields_},)
+        if v.want & capi.POLL_CENSUS:
+            out["census"] = self._census_dict(v.census)
+        if v.want & capi.POLL_REPL_CENSUS:
+            out["repl_census"] = self._repl_census_dict(v.repl_census)
+        out["redone"] = bool(v.state & capi.NODE_POLL_REDONE)
+        return out
 
     def node_outbox(self) -> dict:
         """jg_node_outbox_view as host copies (see `step_node`)."""
         o = capi.NodeOutbox()
         self._check(self.api.node_outbox_view(self._h, C.byref(o)))
+        if self.__dict__.get("_kept_backlog"):  # (kept steps were outstanding: the view served the oldest)
+            self._viewed_backlog = self._kept_backlog.pop(0)
         G, R = self.G, self.R
 
         def arr(p, dt, shape):
@@ -802,21 +848,10 @@ class BatchedRaft(_Hosting):
             return rows, int(total.value)
         return rows, int(total.value), {name: int(getattr(b, name)) for name, _ in capi.CommitBacklog._fields_}
 
-    def poll(self, leaders=None, replicas=None, commits=None, census: bool = False, repl_census: Optional[int] = None,
-             g0: int = 0, n: Optional[int] = None) -> dict:
-        """jg_engine_poll: the parts asked for of one tick over the slots g0 .. g0 + n - 1 in ONE call - one settle, one
-        device pass, one synchronisation - each exactly as its separate method answers it.  A feed argument is None (not
-        asked: its shadow is not touched), True, or that feed's options as a dict or a tuple in this order:
-        leaders (limit, peek); replicas (leave_lag, join_lag, limit, peek); commits (limit, peek, commits_only, backlog).
-        A `replicas` dict that names `now_ms` asks for the TIME rule (watch_replicas_timed; ABI v20): its keys are now_ms,
-        max_behind_ms, caught_lag = 0, join_lag = 0, limit, peek - unless `peek`, the clocks of every slot of the range
-        advance to now_ms, whatever `limit` is; naming leave_lag beside them is a TypeError.
-        `census`: jg_engine_census too; `repl_census`: the lag limit of jg_engine_replication_census, or None.  Returns a
-        dict keyed by the parts asked for: "leaders" / "replicas" (rows, total), "commits" (rows, total) or with backlog
-        (rows, total, backlog), "census" / "repl_census" the dicts of census() / replication_census()."""
+    def _poll_request(self, leaders=None, replicas=None, commits=None, census: bool = False, repl_census: Optional[int] = None,
+                      g0: int = 0, n: Optional[int] = None):
+        """the jg_poll of `poll`'s arguments: (p, what it points at - to be kept alive over the call, {"backlog": asked for})"""
         n = self.G - int(g0) if n is None else int(n)
-        if not hasattr(self.api, "engine_poll"):
-            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_poll")
 
         def options(arg, names, defaults):
             if arg is True:
@@ -865,6 +900,7 @@ class BatchedRaft(_Hosting):
             p.commits = keep["commits"].ctypes.data
             backlog = bool(o["backlog"])
         b, c, rc = capi.CommitBacklog(), capi.Census(), capi.ReplCensus()
+        keep.update(backlog=b, census=c, repl_census=rc)
         if backlog:
             p.backlog = C.pointer(b)
         if census:
@@ -874,6 +910,24 @@ class BatchedRaft(_Hosting):
             p.want |= capi.POLL_REPL_CENSUS
             p.census_lag_limit = int(repl_census)
             p.repl_census = C.pointer(rc)
+        return p, keep, {"backlog": backlog}
+
+    def poll(self, leaders=None, replicas=None, commits=None, census: bool = False, repl_census: Optional[int] = None,
+             g0: int = 0, n: Optional[int] = None) -> dict:
+        """jg_engine_poll: the parts asked for of one tick over the slots g0 .. g0 + n - 1 in ONE call - one settle, one
+        device pass, one synchronisation - each exactly as its separate method answers it.  A feed argument is None (not
+        asked: its shadow is not touched), True, or that feed's options as a dict or a tuple in this order:
+        leaders (limit, peek); replicas (leave_lag, join_lag, limit, peek); commits (limit, peek, commits_only, backlog).
+        A `replicas` dict that names `now_ms` asks for the TIME rule (watch_replicas_timed; ABI v20): its keys are now_ms,
+        max_behind_ms, caught_lag = 0, join_lag = 0, limit, peek - unless `peek`, the clocks of every slot of the range
+        advance to now_ms, whatever `limit` is; naming leave_lag beside them is a TypeError.
+        `census`: jg_engine_census too; `repl_census`: the lag limit of jg_engine_replication_census, or None.  Returns a
+        dict keyed by the parts asked for: "leaders" / "replicas" (rows, total), "commits" (rows, total) or with backlog
+        (rows, total, backlog), "census" / "repl_census" the dicts of census() / replication_census()."""
+        if not hasattr(self.api, "engine_poll"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}engine_poll")
+        p, keep, parts = self._poll_request(leaders, replicas, commits, census, repl_census, g0, n)
+        backlog, b, c, rc = parts["backlog"], keep["backlog"], keep["census"], keep["repl_census"]
         self._check(self.api.engine_poll(self._h, C.byref(p)))
         out = {}
         if leaders is not None:
@@ -885,13 +939,21 @@ class BatchedRaft(_Hosting):
             if backlog:
                 out["commits"] += ({name: int(getattr(b, name)) for name, _ in capi.CommitBacklog._fields_},)
         if census:
-            out["census"] = {name: int(getattr(c, name)) for name, t in capi.Census._fields_ if name != "led_by"}
-            out["census"]["led_by"] = [int(x) for x in c.led_by[:self.R]]
+            out["census"] = self._census_dict(c)
         if repl_census is not None:
-            per_member = ("out_of_sync", "max_lag", "sum_lag")
-            out["repl_census"] = {name: int(getattr(rc, name)) for name, t in capi.ReplCensus._fields_ if name not in per_member}
-            for name in per_member:
-                out["repl_census"][name] = [int(x) for x in getattr(rc, name)[:self.R]]
+            out["repl_census"] = self._repl_census_dict(rc)
+        return out
+
+    def _census_dict(self, c) -> dict:
+        out = {name: int(getattr(c, name)) for name, t in capi.Census._fields_ if name != "led_by"}
+        out["led_by"] = [int(x) for x in c.led_by[:self.R]]
+        return out
+
+    def _repl_census_dict(self, rc) -> dict:
+        per_member = ("out_of_sync", "max_lag", "sum_lag")
+        out = {name: int(getattr(rc, name)) for name, t in capi.ReplCensus._fields_ if name not in per_member}
+        for name in per_member:
+            out[name] = [int(x) for x in getattr(rc, name)[:self.R]]
         return out
 
     def counters(self) -> dict:

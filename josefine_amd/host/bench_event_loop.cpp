@@ -222,6 +222,17 @@ static void run_loop(uint32_t G, uint32_t R, uint32_t T, uint32_t W, const std::
     // t's outputs are read; the same rows reach the same sinks in the same order, the device is never idle in between
     if (const char* f = std::getenv("JG_BENCH_IN_FLIGHT")) loop.in_flight = pipe ? (uint32_t)std::max(1, std::atoi(f)) : 1u;
     if (compact) loop.bus = JG_NODE_COMMON_AE | JG_NODE_FSM_FUSED;
+    // JG_BENCH_POLL (off by default): a poll of all five parts every tick - "step": attached to every tick's step (two ticks in
+    // flight: jg_step_node_polled, the answer handed to a sink with the tick's outputs); "sync": what a loop had before that -
+    // the outstanding steps are viewed, then jg_engine_poll, every tick
+    const char* poll_env = std::getenv("JG_BENCH_POLL");
+    const std::string poll_mode = poll_env ? poll_env : "";
+    BatchedRaft::PollRequest poll_q;
+    poll_q.want = JG_POLL_LEADERS | JG_POLL_REPLICAS | JG_POLL_COMMITS | JG_POLL_CENSUS | JG_POLL_REPL_CENSUS;
+    poll_q.policy = jg_isr_policy{4, 0}, poll_q.census_lag_limit = 4;
+    uint64_t poll_rows = 0, polls = 0;
+    auto poll_sink = [&](const BatchedRaft::PollResult& r, bool) { poll_rows += r.leaders.size() + r.replicas.size() + r.commits.size(), polls++; };
+    if (poll_mode == "step") loop.set_poll(poll_q, poll_sink);
     uint64_t sink = 0, fsm_rows = 0, msg_rows = 0, col_bytes = 0, up_bytes = 0, general = 0;
     double t_sinks = 0;  // (inside the sinks: the consumers' reading of what came home - the rest of a step's time is the engine's calls and their waits)
     raft.fsm_rows_tx = [&](const jg_fsm_row* r, size_t n) {
@@ -417,6 +428,10 @@ static void run_loop(uint32_t G, uint32_t R, uint32_t T, uint32_t W, const std::
         const double ms_c = ms_since(a);
         t_submit += ms_c, a = Clock::now();
         loop.run_until(now);
+        if (poll_mode == "sync") {
+          loop.flush();
+          poll_sink(raft.poll(poll_q), false);
+        }
         const double ms_s = ms_since(a);
         t_step += ms_s;
         if (tick_trace && t >= W)
@@ -437,6 +452,7 @@ static void run_loop(uint32_t G, uint32_t R, uint32_t T, uint32_t W, const std::
       rows_in += n;
     }
     loop.flush();  // (pipelined: the last tick's outputs)
+    if (!poll_mode.empty()) std::fprintf(stderr, "[poll %s] %llu polls, %llu rows\n", poll_mode.c_str(), (unsigned long long)polls, (unsigned long long)poll_rows);
     const Clock::time_point t_end = rv.arrive();
     finished = true;
     out.wall_ms = std::chrono::duration<double, std::milli>(t_end - t_begin).count();

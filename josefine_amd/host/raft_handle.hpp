@@ -437,6 +437,41 @@ class BatchedRaft {
     r.commits.resize(std::min<size_t>(r.commits_total, r.commits.size()));
     return r;
   }
+  // A poll behind a kept node step (jg_step_node_polled / jg_node_poll_view, ABI v21; only callers need a library that has
+  // them): step_node_begin(now_ms, flags, true, true) with `q` attached - the poll is queued behind the step's own kernels,
+  // sees the engine exactly as the step leaves it and comes home on the step's trip; node_poll() hands it out once
+  // step_node_finish has served that step.  The answer is what poll(q) would have returned between that step and the next.
+  void step_node_polled(uint64_t now_ms, uint32_t flags, const PollRequest& q) {
+    flush_rows();
+    static jg_commit_backlog wanted;  // (never written through: the pointer only says that the backlog is wanted)
+    jg_poll p{};
+    p.want = q.want, p.g0 = q.g0, p.n = q.n == UINT32_MAX ? (uint32_t)stores_.size() - q.g0 : q.n;
+    p.leader_flags = q.leaders_peek ? (uint32_t)JG_WATCH_PEEK : 0u;
+    p.replica_flags = q.replicas_peek ? (uint32_t)JG_WATCH_PEEK : 0u;
+    p.commit_flags = (q.commits_peek ? (uint32_t)JG_WATCH_PEEK : 0u) | (q.commits_only ? (uint32_t)JG_WATCH_COMMITS_ONLY : 0u);
+    p.policy = q.policy, p.census_lag_limit = q.census_lag_limit;
+    p.clock = q.timed ? &q.clock : nullptr;
+    p.leaders_cap = std::min<size_t>(q.leaders_limit, p.n), p.replicas_cap = std::min<size_t>(q.replicas_limit, p.n);
+    p.commits_cap = std::min<size_t>(q.commits_limit, p.n);
+    p.backlog = &wanted;
+    check(jg_step_node_polled(e_, now_ms, flags | (uint32_t)JG_NODE_ASYNC | (uint32_t)JG_NODE_KEEP, &p));
+    step_blocks_.emplace_back();
+    step_blocks_.back().swap(pending_blocks_);  // (as step_node_begin)
+  }
+  // the poll of the kept step step_node_finish served last; *polled: that step carried one; *redone: JG_NODE_POLL_REDONE
+  PollResult node_poll(bool* polled = nullptr, bool* redone = nullptr) {
+    jg_node_poll v{};
+    check(jg_node_poll_view(e_, &v));
+    PollResult r;
+    if (v.leaders_n) r.leaders.assign(v.leaders, v.leaders + v.leaders_n);
+    if (v.replicas_n) r.replicas.assign(v.replicas, v.replicas + v.replicas_n);
+    if (v.commits_n) r.commits.assign(v.commits, v.commits + v.commits_n);
+    r.leaders_total = v.leaders_total, r.replicas_total = v.replicas_total, r.commits_total = v.commits_total;
+    r.backlog = v.backlog, r.census = v.census, r.repl_census = v.repl_census;
+    if (polled) *polled = v.want != 0;
+    if (redone) *redone = (v.state & JG_NODE_POLL_REDONE) != 0;
+    return r;
+  }
   // commit rows as the FSM rows a dense step does not queue: every row that is COMMITTED and not REWOUND becomes
   // JG_FSM_APPLY_LEADER (where LEADS: keys (a, b]) or JG_FSM_APPLY_FOLLOWER (keys [a, b)) {a = commit_from, b = commit}; a
   // rewound row has no range - the consumer resynchronises its store from the row's commit / head
@@ -961,6 +996,25 @@ class BatchedEventLoop {
   // word per partition where the followers' agree - and / or JG_NODE_FSM_FUSED - a leader's fsm_tx rows of a step as one
   // row; both are expanded again by BatchedRaft before rpc_tx / fsm_tx see them (a column / row sink sees the compact form)
   uint32_t bus = 0;
+  // The feeds of a loop with two ticks in flight (ABI v21; only a caller of set_poll needs a library that has
+  // jg_step_node_polled / jg_node_poll_view): with in_flight >= 2 every tick's step carries `q` (under the time rule with the
+  // step's own time as clock.now_ms), and `sink` receives the PollResult when that tick's outputs are consumed - after its
+  // fsm_tx / rpc_tx rows and columns.  A template, so that a program that never polls does not name the entry points.
+  using PollSink = std::function<void(const BatchedRaft::PollResult&, bool redone)>;
+  template <class Raft = BatchedRaft>
+  void set_poll(const typename Raft::PollRequest& q, PollSink sink) {
+    Raft* const r = &raft_;
+    begin_polled_ = [r, q](uint64_t at, uint32_t flags) {
+      typename Raft::PollRequest qq = q;
+      if (qq.timed) qq.clock.now_ms = at;
+      r->step_node_polled(at, flags, qq);
+    };
+    view_polled_ = [r, sink]() {
+      bool polled = false, redone = false;
+      const typename Raft::PollResult res = r->node_poll(&polled, &redone);
+      if (polled && sink) sink(res, redone);
+    };
+  }
 
   explicit BatchedEventLoop(BatchedRaft& raft, uint32_t n_groups) : raft_(raft), G_(n_groups), answers_to_(n_groups, 0) {
     raft_.rpc_tx = [this](const Message& m) { on_message(m); };
@@ -1056,7 +1110,10 @@ class BatchedEventLoop {
     if (dense) {
       if (!in_.empty()) raft_.submit_rows(in_.view());
       in_.clear();
-      raft_.step_node_begin(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u), pipelined, two);
+      const bool polled = two && begin_polled_;
+      if (polled) begin_polled_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u));
+      else raft_.step_node_begin(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u), pipelined, two);
+      polled_steps_.push_back(polled);
       answers_of_step_.push_back(std::move(answers));  // (once the step has begun: one entry per open step, whatever begin() throws)
       last_at_ = at;
       if (pipelined) return;
@@ -1076,6 +1133,11 @@ class BatchedEventLoop {
       answers_of_step_.pop_front();
     }
     raft_.step_node_finish(&answers_to_);
+    if (!polled_steps_.empty()) {
+      const bool polled = polled_steps_.front();
+      polled_steps_.pop_front();
+      if (polled) view_polled_();
+    }
   }
   // Address::Local messages (server.rs:143) are applied before anything new is accepted
   void drain_local(uint64_t at) {
@@ -1141,6 +1203,9 @@ class BatchedEventLoop {
   std::map<std::pair<uint32_t, uint64_t>, std::vector<uint8_t>> proxied_;
   std::vector<NodeId> answers_to_;                        // per partition: who its Heartbeat / AppendEntries came from
   std::deque<std::vector<std::pair<uint32_t, NodeId>>> answers_of_step_;  // ... as noted by the steps begun and not finished
+  std::function<void(uint64_t, uint32_t)> begin_polled_;  // set_poll: the step with the request attached ...
+  std::function<void()> view_polled_;                      // ... and its answer to the sink
+  std::deque<bool> polled_steps_;                          // per open step: was it begun with the poll
   std::deque<Message> local_;
   std::map<uint64_t, Response> requests_;
   std::map<std::pair<uint32_t, BlockId>, uint64_t> notifications_;
