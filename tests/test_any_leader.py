@@ -130,7 +130,7 @@ def ref_py_engine(*a, **kw):
     return RefEngine(*a, **kw)
 
 
-@pytest.mark.parametrize("R", [3, 5])
+@pytest.mark.parametrize("R", [3, 4, 5, 6])
 def test_any_leader_cluster_oracle_vs_ref_py(R):
     """The round's statement over the C++ oracle and over the independent Python reading of the Rust: every column of
     every node after every round, with two leaders in some groups and leaders failing."""
@@ -152,7 +152,7 @@ def test_any_leader_cluster_oracle_vs_ref_py(R):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("R,percent,dual", [(3, 3, 0), (3, 3, 9), (5, 2, 13), (2, 0, 5), (3, -4, 0)])
+@pytest.mark.parametrize("R,percent,dual", [(3, 3, 0), (3, 3, 9), (5, 2, 13), (2, 0, 5), (3, -4, 0), (4, 2, 11), (6, 2, 13)])
 def test_any_leader_cluster_device_parity(R, percent, dual):
     """(percent < 0: that many percent per round, the groups RE-CREATED - JG_CMD_RECREATE - and failing any number of times)"""
     from josefine_amd import DenseCluster as LibCluster
@@ -175,7 +175,7 @@ def test_any_leader_cluster_device_parity(R, percent, dual):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("R", [3, 5])
+@pytest.mark.parametrize("R", [3, 5, 6])
 def test_any_leader_rounds_replayed_as_a_graph(R):
     """jg_dense_cluster_rounds with per-partition leadership (five launches per round, replayed as one hipGraph) == the
     statement's rounds: state, and every row the rounds queued (nothing is routed here)."""

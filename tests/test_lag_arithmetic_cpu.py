@@ -51,7 +51,9 @@ extern "C" int lag_tick(int R, uint32_t s, uint32_t f, uint64_t w0, uint64_t hea
     case 3: return run<3>(s, f, w0, head0, n_app, a, out);
     case 4: return run<4>(s, f, w0, head0, n_app, a, out);
     case 5: return run<5>(s, f, w0, head0, n_app, a, out);
+    case 6: return run<6>(s, f, w0, head0, n_app, a, out);
     case 7: return run<7>(s, f, w0, head0, n_app, a, out);
+    case 8: return run<8>(s, f, w0, head0, n_app, a, out);
     default: return -1;
   }
 }
@@ -65,6 +67,8 @@ extern "C" int lag_pre(int R, uint32_t s, uint64_t w0, uint64_t head0, const uin
   switch (R) {
     case 3: return run_pre<3>(s, w0, head0, a, pre, adv);
     case 5: return run_pre<5>(s, w0, head0, a, pre, adv);
+    case 6: return run_pre<6>(s, w0, head0, a, pre, adv);
+    case 8: return run_pre<8>(s, w0, head0, a, pre, adv);
     default: return -1;
   }
 }
@@ -107,9 +111,14 @@ def _leaders(G, R, H, v, own):
     e = oracle_engine(G, R, seed=1, self_slots=np.full(G, own, np.uint8), flags=capi.CFG_SEPARATE_COMMIT_KEY)
     elect_all(e)
     others = [r for r in range(R) if r != own]
-    acks = np.full((R, G), NO, np.uint64)
-    acks[own] = H
-    e.step_dense_acks(acks)  # H appends, self-acked (leader.rs:177-197)
+    left = np.array(H, np.uint64)
+    while True:  # H appends, self-acked (leader.rs:177-197), in ticks of fewer than JG_MAX_DENSE_APPENDS
+        acks = np.full((R, G), NO, np.uint64)
+        acks[own] = np.minimum(left, np.uint64(capi.MAX_DENSE_APPENDS - 1))
+        e.step_dense_acks(acks)
+        left = left - acks[own]
+        if not left.any():
+            break
     acks = np.full((R, G), NO, np.uint64)
     acks[own] = 0
     acks[others] = v
@@ -119,8 +128,11 @@ def _leaders(G, R, H, v, own):
     return e
 
 
-def _check(lag, R, H, v, n_app, a, own=0):
-    """states (H, v) x inputs (n_app, a): the kernel's arithmetic against the oracle, group by group"""
+def _check(lag, R, H, v, n_app, a, own=0, edges=None):
+    """states (H, v) x inputs (n_app, a): the kernel's arithmetic against the oracle, group by group.  `edges`: a dict - the
+    states reach the end of a lag field, where the function also refuses a lag that leaves its field and a commit index
+    that is or becomes an escape; the refusals are then held to all four documented reasons (stated on absolute heads,
+    not on lags), `adv` to the oracle's commit index, and the dict receives how many ticks each reason refused"""
     G = len(H)
     others = [r for r in range(R) if r != own]
     e = _leaders(G, R, H, v, own)
@@ -135,6 +147,7 @@ def _check(lag, R, H, v, n_app, a, own=0):
     ok = np.zeros(G, bool)
     got = np.zeros((G, R + 3), np.uint64)  # match[0..R), commit, head, repl bits
     dec = np.zeros(G, np.int64)
+    adv, cwide = np.zeros(G, np.uint64), np.zeros(G, bool)
     out = (C.c_uint64 * 6)()
     for g in range(G):
         w0 = 0
@@ -151,18 +164,41 @@ def _check(lag, R, H, v, n_app, a, own=0):
             got[g][R + 1] = head1
             got[g][R + 2] = (out[2] >> 8) & 0xFF
             dec[g] = out[3]
+            adv[g], cwide[g] = out[4], bool(out[5])
     # refused exactly where documented: an acknowledgement above the head it meets (the appends come first), or one for a
     # slot whose lag is an escape code (the caller's domain: none in the small states, the BEHIND slot in the large one)
     above = ((a != NO) & (a > (H + n_app)[None, :])).any(axis=0)
     wide0 = np.array([[lag.lag_wide(lag.lag_encode(int(match0[r][g]), int(head0[g]), R), R) for g in range(G)] for r in range(R)], bool)
     acked_wide = (wide0[others] & (a != NO)).any(axis=0)
-    assert np.array_equal(~ok, above | acked_wide), np.nonzero(~ok != (above | acked_wide))[0][:8]
+    refused = above | acked_wide
+    if edges is not None:
+        # ... and, at the end of a field: a lag that leaves its field (a slot that was inside it and is BEHIND or further
+        # below the new head), a commit index that is or becomes an escape (head - commit at or above BEHIND after the
+        # tick) - on the heads the reference would hold after this tick (progress.rs:133-140, 48-60; leader.rs:89-92)
+        behind = np.uint64(lag.lag_behind(R))
+        head1 = (H + n_app).astype(np.uint64)
+        m1 = match0.astype(np.uint64).copy()
+        m1[others] = np.where(a != NO, np.maximum(m1[others], a), m1[others])
+        m1[own] = np.where(n_app > 0, head1, m1[own])
+        leaving = (~wide0 & (head1[None, :] - np.minimum(m1, head1[None, :]) >= behind)).any(axis=0)
+        q = np.sort(m1, axis=0)[::-1][R // 2]
+        escaped = head1 - np.maximum(commit0.astype(np.uint64), np.minimum(q, head1)) >= behind
+        for name, m in (("an ack above the head", above), ("an ack for a BEHIND slot", acked_wide & ~above),
+                        ("a lag leaving its field", leaving & ~above & ~acked_wide),
+                        ("an escaped commit", escaped & ~above & ~acked_wide & ~leaving)):
+            edges[name] = edges.get(name, 0) + int(m.sum())
+        refused = refused | leaving | escaped
+    assert np.array_equal(~ok, refused), np.nonzero(~ok != refused)[0][:8]
     # the oracle's side: the same tick through Leader::commit; groups the kernel refused get an empty tick (no decisions)
     acks[:, ~ok] = NO
     acks[own, ~ok] = 0
     d0 = e.counters()["decisions"]
     e.step_dense_acks(acks)
     assert not e.read("fault").any()
+    if edges is not None:
+        m = ok & ~cwide  # (adv is meaningless where the commit index was in the wide column: no such tick is served here)
+        assert np.array_equal(adv[m], (e.read("commit") - commit0)[m]), np.nonzero(adv != e.read("commit") - commit0)[0][:8]
+        assert not (ok & cwide).any()
     want_match = np.stack([e.read("match", replica=r) for r in range(R)])
     sel = ok
     for r in range(R):
@@ -191,7 +227,7 @@ def test_lag_tick_exhaustive_small_domain_r3(lag):
 
 def test_lag_tick_sampled_r5_and_r7(lag):
     rng = np.random.default_rng(5)
-    for R, hmax in ((5, 6), (5, 40), (7, 40), (2, 40), (4, 40)):
+    for R, hmax in ((5, 6), (5, 40), (7, 40), (2, 40), (4, 40), (6, 40), (8, 40)):
         for own in range(R):  # (the majority networks treat the slots differently: every place of the own slot)
             G = 3000
             H = rng.integers(0, hmax, G).astype(np.uint64)
@@ -200,6 +236,50 @@ def test_lag_tick_sampled_r5_and_r7(lag):
             a = np.stack([np.where(rng.random(G) < 0.25, NO, rng.integers(0, H + n + 2).astype(np.uint64)) for _ in range(R - 1)]).astype(np.uint64)
             served = _check(lag, R, H, v, n, a, own=own)
             assert served > G // 2
+
+
+# how much of the product an own slot sees at the long fields (every combination at some own slot): the oracle appends
+# block by block, 2 097 153 and 65 537 of them per group here
+EDGE_STRIDE = {2: 4, 3: 3}
+
+
+@pytest.mark.parametrize("R", [2, 3, 4, 5, 6, 7, 8])
+def test_lag_tick_field_edges(lag, R):
+    """Every replica count at the end of its lag field: leaders whose head is BEHIND + 3, with k other members (k = 1,
+    R / 2 - 1, R / 2 - one short of a quorum at even R - and R - 1) at a lag of BEHIND - 2, BEHIND - 1 (the last that fits),
+    BEHIND and BEHIND + 1 and the rest 0-2 blocks behind; ticks of 0, 1, 2 appends in which those members say nothing,
+    repeat their old progress, or acknowledge the old head, the new head or one above it.  Where jg_lag_tick serves the
+    tick, word, head, flags, decisions and adv equal the oracle's; where it refuses, the reason is a documented one, and
+    each of them occurs.  At R = 2 every fourth combination runs per own slot (half of them in all: 30 groups), at R = 3
+    every third (all of them over the three own slots)."""
+    behind = int(lag.lag_behind(R))
+    assert behind == (1 << (64 // (R + 1))) - 2
+    H0 = behind + 3
+    ks = sorted({k for k in (1, R // 2 - 1, R // 2, R - 1) if 1 <= k <= R - 1})
+    combos = list(itertools.product((behind - 2, behind - 1, behind, behind + 1), (0, 1, 2), range(5), ks))
+    stride = EDGE_STRIDE.get(R, 1)
+    reasons, served = {}, 0
+    for own in range(R):
+        rows = [(i, c) for i, c in enumerate(combos) if i % stride == own % stride]
+        G = len(rows)
+        H = np.full(G, H0, np.uint64)
+        v = np.zeros((R - 1, G), np.uint64)
+        n = np.zeros(G, np.uint64)
+        a = np.full((R - 1, G), NO, np.uint64)
+        for g, (i, (d, n_app, kind, k)) in enumerate(rows):
+            n[g] = n_app
+            at_edge = {(i + j) % (R - 1) for j in range(k)}  # which of the others: it moves with the combination
+            for j in range(R - 1):
+                if j in at_edge:
+                    v[j, g] = H0 - d
+                    a[j, g] = (int(NO), H0 - d, H0, H0 + n_app, H0 + n_app + 1)[kind]
+                else:
+                    v[j, g] = H0 - (i + j) % 3
+                    a[j, g] = H0 + n_app if (i + j) % 2 else int(NO)
+        served += _check(lag, R, H, v, n, a, own=own, edges=reasons)
+    total = sum(1 for own in range(R) for i in range(len(combos)) if i % stride == own % stride)
+    assert all(reasons[k] > 0 for k in ("an ack above the head", "an ack for a BEHIND slot", "a lag leaving its field", "an escaped commit")), reasons
+    assert served > total // 8 and served + sum(reasons.values()) == total, (served, reasons, total)
 
 
 def test_lag_tick_a_follower_too_far_behind_stays_in_lag_space_r3(lag):
