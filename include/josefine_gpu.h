@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 21u /* v21: jg_step_node_polled / jg_node_poll_view (a poll behind a kept node step: the feeds with two ticks in flight); v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 22u /* v22: jg_engine_await_open / jg_engine_await_blocks / jg_engine_watch_completions (the completion feed: fsm::Driver's notifications on the device); v21: jg_step_node_polled / jg_node_poll_view (a poll behind a kept node step: the feeds with two ticks in flight); v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -735,6 +735,88 @@ typedef struct jg_commit_backlog {     /* over ALL slots of the range that diffe
 } jg_commit_backlog;
 int jg_engine_watch_commits(jg_engine* e, uint32_t flags, uint32_t g0, uint32_t n, jg_commit_row* out, size_t cap, size_t* total,
                             jg_commit_backlog* backlog /* may be NULL */);
+
+/* ---- the completion feed: fsm::Driver's notifications on the device (ABI v22) --------------------------
+ * "Which of the produce requests I am holding can be answered now, and how?" - the reference keeps
+ * notifications: HashMap<BlockId, (Address, ClientRequestId)> (src/raft/fsm.rs:35): Instruction::Notify
+ * (leader.rs:184-188) inserts, every Instruction::Apply looks its block id up and sends the
+ * ClientResponse (fsm.rs:65-76).  On the dense path a caller would expand every commit row into single
+ * block keys and probe a map once per key.  Here the WAITERS (partition, block id, token) live in device
+ * memory and one call per tick answers which tokens are done, and why - applied, lost (not leader any
+ * more: retry elsewhere), expired (timed out): a produce purgatory.
+ *
+ * jg_engine_await_open (re)sizes the TABLE to `capacity` waiters (two buffers of 48 bytes a waiter, a
+ * verdict byte each, the scan's scratch); 0 frees it.  JG_EINVAL while waiters are outstanding.
+ *
+ * jg_engine_await_blocks registers n waiters behind the table's end, ALL OR NOTHING: JG_EINVAL - with
+ * nothing registered - for a null argument, a group >= G, nonzero flags or reserved, block_id == 0 (the
+ * reference skips block 0, fsm.rs:61), no open table; JG_ECAPACITY when outstanding + n > capacity; n == 0
+ * is JG_OK.  token is opaque and returned as given.  term == 0 selects the reference's rule, term != 0
+ * guards the waiter by leadership.  deadline_ms == 0: the waiter never expires.
+ *
+ * A waiter's VERDICT is decided at a watch, from its slot's state as jg_read_state would return it then -
+ * role, fault, JG_FIELD_TERM, JG_FIELD_COMMIT (decoded exactly as the commit feed and the point queries
+ * do), JG_FIELD_HEAD.  The first rule that matches wins:
+ *   1. fault 255 -> JG_DONE_LOST | JG_DONE_VACANT; any other nonzero fault -> JG_DONE_LOST | JG_DONE_FAULTED
+ *   2. term != 0 and (role is not leader or JG_FIELD_TERM != term) -> JG_DONE_LOST.  Deliberately BEFORE
+ *      the applied test: a block that committed under a later leadership cannot be told from a different
+ *      block with the same id.  The client retries: at-least-once, as Kafka gives
+ *   3. applied -> JG_DONE_APPLIED: the slot leads (role leader, fault 0) and block_id <= commit, or it does
+ *      not lead and block_id < commit - the two key conventions of the commit feed, leader (commit_from,
+ *      commit], follower [commit_from, commit), applied from genesis
+ *   4. deadline_ms != 0 and now_ms >= deadline_ms -> JG_DONE_EXPIRED
+ *   5. otherwise the waiter keeps waiting
+ *
+ * TWO DEPARTURES from the reference.  Every registered waiter is answered exactly once: registering a key
+ * twice answers both, where the reference's map would forget the first (its leader never does this:
+ * Chain::append draws a fresh id each time).  And applied is a WATERMARK, not an event: an id already
+ * under the watermark at registration completes at the next watch, where the reference's Apply for it
+ * has passed and it would never answer (Notify always precedes the commit that applies it, so the
+ * reference's own callers cannot tell the difference).
+ *
+ * jg_engine_watch_completions: the table keeps REGISTRATION ORDER.  *total = the done waiters; `out`
+ * (host memory) receives the first min(cap, total) of them in that order; cap 0: counts only.  The watch
+ * removes exactly the delivered waiters, the survivors keep their relative order; a done waiter beyond
+ * cap is a survivor.  JG_WATCH_PEEK delivers the same rows and removes nothing.  A row: group, the
+ * verdict in `state`, role / fault / self_slot, JG_FIELD_TERM / COMMIT / HEAD now, token and block_id as
+ * registered.  stats, where not NULL: waiting / done / applied / lost / expired describe the state BEFORE
+ * this call's delivery over EVERY waiter (done == *total), left = the waiters outstanding after the call.
+ * Integers, exact whatever order the reduction runs in.
+ *
+ * Both calls READ under the rules of the other feeds: JG_NODE_ASYNC steps are settled first; nothing a
+ * step, a drain, a read or another feed can observe changes; JG_EINVAL - with nothing written - while
+ * kept node steps are outstanding, for an unknown flag, for now_ms == UINT64_MAX, a null `e` / `total`, a
+ * null `out` with cap > 0.  A watch on an engine without a table is JG_OK with total 0.  A multi-device
+ * parent handle buckets the rows by owner shard, stably; each shard has a table of its own and `capacity`
+ * is per shard; a watch sizes every shard by a peek (the stats are the shards' sums), then each shard
+ * delivers into what is left of `cap`, in shard order, `group` the parent's index; a shard behind the
+ * point where cap ran out keeps its waiters. */
+enum { JG_DONE_APPLIED = 1u, JG_DONE_LOST = 2u, JG_DONE_EXPIRED = 4u,
+       JG_DONE_VACANT = 8u, JG_DONE_FAULTED = 16u };   /* jg_done_row.state */
+typedef struct jg_await_row {          /* 48 bytes: three 16-byte pieces */
+  uint32_t group;                      /* local slot (a sharded handle: index within the parent) */
+  uint32_t flags;                      /* must be 0 */
+  uint64_t token;                      /* opaque: returned as given */
+  uint64_t block_id;                   /* != 0 */
+  uint64_t term;                       /* 0: the reference's rule; else the leadership the waiter is guarded by */
+  uint64_t deadline_ms;                /* 0: never expires */
+  uint64_t reserved;                   /* must be 0 */
+} jg_await_row;
+typedef struct jg_done_row {           /* 48 bytes: three 16-byte pieces */
+  uint32_t group;                      /* local slot (a sharded handle: index within the parent) */
+  uint8_t state, role, fault, self_slot;   /* JG_DONE_* bits; JG_FIELD_ROLE / FAULT / SELF_SLOT now */
+  uint64_t token;
+  uint64_t block_id, term_now;         /* as registered / JG_FIELD_TERM now */
+  uint64_t commit_now, head_now;       /* JG_FIELD_COMMIT / JG_FIELD_HEAD now */
+} jg_done_row;
+typedef struct jg_await_stats {
+  uint64_t waiting, done, applied, lost, expired;   /* before this call's delivery, over every waiter */
+  uint64_t left;                                    /* outstanding after the call */
+} jg_await_stats;
+int jg_engine_await_open(jg_engine* e, size_t capacity);
+int jg_engine_await_blocks(jg_engine* e, const jg_await_row* rows, size_t n);
+int jg_engine_watch_completions(jg_engine* e, uint32_t flags, uint64_t now_ms, jg_done_row* out, size_t cap, size_t* total,
+                                jg_await_stats* stats /* may be NULL */);
 
 /* ---- one poll per tick: the three feeds and the two censuses in one call (ABI v18) --------------------
  * An event loop that consumes several feeds asks them of the same slots once per tick.  Asked separately

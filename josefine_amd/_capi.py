@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -252,6 +252,16 @@ class ReplCensus(C.Structure):
                 ("sum_lag", C.c_uint64 * MAX_REPLICAS), ("max_uncommitted", C.c_uint64)]
 
 
+# jg_done_row.state
+DONE_APPLIED, DONE_LOST, DONE_EXPIRED, DONE_VACANT, DONE_FAULTED = 1, 2, 4, 8, 16
+
+
+class AwaitStats(C.Structure):
+    """jg_await_stats."""
+    _fields_ = [("waiting", C.c_uint64), ("done", C.c_uint64), ("applied", C.c_uint64), ("lost", C.c_uint64),
+                ("expired", C.c_uint64), ("left", C.c_uint64)]
+
+
 POLL_LEADERS, POLL_REPLICAS, POLL_COMMITS, POLL_CENSUS, POLL_REPL_CENSUS = 1, 2, 4, 8, 16  # jg_poll.want
 
 
@@ -329,6 +339,11 @@ GROUP_STATE_DTYPE = [("group", "<u4"), ("known_leader", "<u4"), ("term", "<u8"),
 # jg_commit_row: a row of jg_engine_watch_commits (48 bytes)
 COMMIT_ROW_DTYPE = [("group", "<u4"), ("role", "u1"), ("state", "u1"), ("fault", "u1"), ("self_slot", "u1"), ("term", "<u8"),
                     ("commit_from", "<u8"), ("commit", "<u8"), ("head_from", "<u8"), ("head", "<u8")]
+# jg_await_row / jg_done_row: a waiter and a row of jg_engine_watch_completions (48 bytes each)
+AWAIT_ROW_DTYPE = [("group", "<u4"), ("flags", "<u4"), ("token", "<u8"), ("block_id", "<u8"), ("term", "<u8"),
+                   ("deadline_ms", "<u8"), ("reserved", "<u8")]
+DONE_ROW_DTYPE = [("group", "<u4"), ("state", "u1"), ("role", "u1"), ("fault", "u1"), ("self_slot", "u1"), ("token", "<u8"),
+                  ("block_id", "<u8"), ("term_now", "<u8"), ("commit_now", "<u8"), ("head_now", "<u8")]
 
 _P = C.c_void_p
 
@@ -413,6 +428,10 @@ class Api:
         "engine_lookup_groups": (C.c_int, [_P, C.POINTER(GroupSet), C.c_void_p, C.c_void_p]),
         "engine_watch_commits": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                            C.POINTER(CommitBacklog)]),
+        "engine_await_open": (C.c_int, [_P, C.c_size_t]),
+        "engine_await_blocks": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+        "engine_watch_completions": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                               C.POINTER(AwaitStats)]),
         "engine_poll": (C.c_int, [_P, C.POINTER(Poll)]),
         "step_node_polled": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.POINTER(Poll)]),
         "node_poll_view": (C.c_int, [_P, C.POINTER(NodePoll)]),
@@ -466,4 +485,5 @@ HEADER_SYMBOLS = [
     "jg_engine_poll",
     "jg_step_node_polled", "jg_node_poll_view",
     "jg_engine_watch_replicas_timed",
+    "jg_engine_await_open", "jg_engine_await_blocks", "jg_engine_watch_completions",
 ]

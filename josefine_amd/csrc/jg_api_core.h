@@ -333,6 +333,23 @@ struct jg_engine {
   // jg_engine_watch_commits: the (commit, head) last delivered per slot ([G] records of jg_commits.h, zero = "genesis
   // only"); allocated at the first watch
   uint4* commit_shadow = nullptr;
+  // jg_engine_await_open: the completion feed's table (jg_await.h) - two buffers of `cap` waiters, of which buf[cur] holds
+  // the n outstanding ones in registration order, a verdict byte per waiter, the tile counts / prefixes, the partial stat
+  // records and one block for the total, the stats and the scan job
+  struct AwaitTable {
+    uint4* buf[2] = {nullptr, nullptr};
+    uint8_t* verdict = nullptr;
+    uint64_t *bsum = nullptr, *part = nullptr;
+    char* misc = nullptr;
+    size_t cap = 0, n = 0;
+    int cur = 0;
+    void release() {
+      for (void* p : {(void*)buf[0], (void*)buf[1], (void*)verdict, (void*)bsum, (void*)part, (void*)misc})
+        if (p) (void)hipFree(p);
+      buf[0] = buf[1] = nullptr, verdict = nullptr, bsum = part = nullptr, misc = nullptr;
+      cap = n = 0, cur = 0;
+    }
+  } await;
   // two sets of the device-side fault / exceptional-row queues: kernels append to [cur_set] while
   // the other one is being copied out
   JgFaultRec* fq[2] = {nullptr, nullptr};

@@ -173,6 +173,7 @@ void jg_engine_destroy(jg_engine* e) {
   e->arenas[0].destroy();
   e->arenas[1].destroy();
   for (void* p : e->allocs) (void)hipFree(p);
+  e->await.release();
   if (e->d_acks_staging) (void)hipFree(e->d_acks_staging);
   if (e->stage) (void)hipHostFree(e->stage);
   if (e->h_status) (void)hipHostFree(e->h_status);

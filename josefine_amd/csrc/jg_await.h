@@ -1,0 +1,181 @@
+// jg_await.h — gfx950 kernels of jg_engine_watch_completions: the completion feed, fsm::Driver's notifications
+// (src/raft/fsm.rs:35, 56-84) as a table of waiters in device memory.  A WAITER is 48 bytes in three 16-byte pieces
+// {group, flags, token} {block_id, term} {deadline_ms, reserved}; the table keeps them in registration order, in one of two
+// buffers.  A watch decides every waiter's VERDICT from its slot's columns as jg_read_state returns them (the commit
+// decoded with jg_read_commit, as the commit feed and the point queries do), delivers the first `cap` done waiters in
+// table order and compacts the survivors, order kept, into the other buffer.
+//
+//   k_await_count      one lane per waiter, a tile of JG_AWT_TILE waiters at a time: the waiter as three 16-byte loads,
+//                      then its slot's columns as a gather in the manner of k_lookup - the flag word, term, head, mlag,
+//                      commit, run_hi, all issued before the first use (one round trip; 44 bytes used of six 64-byte
+//                      sectors) - the verdict byte stored, "done" counted by one 64-bit __ballot and a __popcll per wave,
+//                      the wave counts through LDS into the tile count.  A workgroup takes the tiles b, b + grid, ..., so
+//                      there are at most JG_AWT_PARTS partial stat records (counts by ballots: exact in any order)
+//   k_scan_block_sums  (jg_sparse.h) the tile counts -> exclusive prefixes and the total
+//   k_await_stats_sum  the partial records -> the stats (one workgroup)
+//   k_await_write      reads verdict and prefix: the rank among the done = ballot bits below + wave offset through LDS +
+//                      tile prefix.  Done and rank < cap: DELIVERED - the slot's columns gathered again (for delivered rows
+//                      only: the count pass keeps no side record) and the row written as three 16-byte stores.  Else,
+//                      unless peeking, the waiter is copied to position i - min(rank, cap) of the other buffer: one scan
+//                      serves both ranks.  Nothing to deliver (the total is 0, or cap is): every workgroup returns after
+//                      its first load
+//
+// No atomics, no scratch.  Nothing here writes a column of the state machine: the only stores are the verdict bytes, the
+// tile counts, the partial records, the rows and the other buffer.
+#pragma once
+#include "jg_device.h"
+#include "jg_lookup.h"  // jg_u32x4
+#include "jg_read.h"    // jg_read_commit
+#include "jg_sparse.h"  // JgScanJob, k_scan_block_sums
+#include "jg_watch.h"   // jg_wave_sum64
+
+#define JG_AWT_TILE JG_BLOCK  // waiters per tile of the passes: one lane per waiter
+// the most workgroups - partial stat records - of the count pass: four a CU on 256 CUs (JG_CMT_PARTS)
+#define JG_AWT_PARTS 1024u
+#define JG_AWT_WORDS 5u  // waiting, done, applied, lost, expired: the first five words of jg_await_stats (`left` is the host's)
+static_assert(sizeof(jg_await_stats) == (JG_AWT_WORDS + 1) * 8, "jg_await_stats is the stat words in order, then left");
+static_assert(sizeof(jg_await_row) == 48, "jg_await_row is three 16-byte pieces");
+static_assert(sizeof(jg_done_row) == 48, "jg_done_row is three 16-byte pieces");
+
+struct JgAwaitArgs {
+  uint32_t n;      // waiters outstanding: the table is tab[0 .. n)
+  uint32_t add;    // added to every group written (a shard's first global slot)
+  uint32_t peek;   // 1: rows only, nothing is removed
+  uint32_t tiles;  // tiles of JG_AWT_TILE waiters
+  uint32_t parts;  // workgroups of k_await_count (<= JG_AWT_PARTS)
+  uint32_t pad;
+  uint64_t now;           // now_ms
+  uint64_t cap;           // rows the caller takes
+  const uint4* tab;       // [n][3] the waiters, registration order
+  uint4* dst;             // [n][3] the other buffer: the survivors, order kept
+  uint8_t* verdict;       // [n] 0: waits; else the row's JG_DONE_* bits
+  uint64_t* bsum;         // [tiles] the tile counts of done waiters, then (k_scan_block_sums) their exclusive prefixes
+  uint64_t* part;         // [parts][JG_AWT_WORDS]
+  uint64_t* sum;          // [JG_AWT_WORDS] the stats
+  const uint64_t* total;  // [1] done waiters of the table (k_scan_block_sums)
+  uint4* out;             // [cap] rows of three 16-byte pieces (device)
+};
+
+__device__ __forceinline__ uint64_t jg_awt_u64(uint32_t lo, uint32_t hi) { return (uint64_t)lo | (uint64_t)hi << 32; }
+
+// The verdict of a waiter (block_id, term, deadline) on a slot in (role, fault, term_now, commit): the first rule wins.
+//   1. vacant -> LOST | VACANT; any other fault -> LOST | FAULTED
+//   2. a guarded waiter (term != 0) whose slot is not the leader of that term any more -> LOST.  Before the applied test on
+//      purpose: a block that committed under a later leadership cannot be told from a different block with the same id
+//   3. applied - the two key conventions of the commit feed from genesis: a leader's Apply keys are (.., commit], a
+//      follower's [.., commit)
+//   4. past its deadline -> EXPIRED
+__device__ __forceinline__ uint32_t jg_await_verdict(uint32_t role, uint32_t fault, uint64_t term_now, uint64_t commit, uint64_t block_id,
+                                                     uint64_t term, uint64_t deadline, uint64_t now) {
+  if (fault == JG_FAULT_VACANT) return JG_DONE_LOST | JG_DONE_VACANT;
+  if (fault) return JG_DONE_LOST | JG_DONE_FAULTED;
+  const bool leads = role == JG_ROLE_LEADER;
+  if (term && (!leads || term_now != term)) return JG_DONE_LOST;
+  if (leads ? block_id <= commit : block_id < commit) return JG_DONE_APPLIED;
+  if (deadline && now >= deadline) return JG_DONE_EXPIRED;
+  return 0u;
+}
+
+__global__ __launch_bounds__(JG_BLOCK) void k_await_count(JgDev d, JgAwaitArgs a) {
+  __shared__ uint32_t wave_n[JG_BLOCK / 64];
+  __shared__ uint64_t wave_b[JG_BLOCK / 64][JG_AWT_WORDS];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t bc[JG_AWT_WORDS] = {0u, 0u, 0u, 0u, 0u};  // wave-uniform (every lane adds the same popcount)
+  for (uint32_t tile = blockIdx.x; tile < a.tiles; tile += a.parts) {  // (uniform over the workgroup)
+    const uint32_t i = tile * JG_AWT_TILE + threadIdx.x;
+    const bool in = i < a.n;
+    const size_t at = (size_t)(in ? i : 0u) * 3;
+    const uint4 w0 = a.tab[at], w1 = a.tab[at + 1], w2 = a.tab[at + 2];
+    const uint32_t g = w0.x < d.G ? w0.x : 0u;  // (checked at registration: never taken)
+    // one round trip: the six unconditional loads of the slot, back to back
+    const uint32_t f = d.flags[g];
+    const uint64_t term_now = d.term[g], head = d.head[g], pw = d.mlag[g], col = d.commit[g], run_hi = d.run_hi[g];
+    const uint64_t commit = jg_read_commit(d, g, f);  // (its loads are the ones above: nothing was stored since)
+    // (the loads stay up there: without an unconditional use the compiler sinks one behind the branch on the role)
+    asm volatile("" ::"v"(f), "v"(term_now), "v"(head), "v"(pw), "v"(col), "v"(run_hi));
+    const uint32_t role = f & JGF_ROLE_MASK, fault = (f & JGF_FAULT_MASK) >> JGF_FAULT_SHIFT;
+    const uint32_t v = in ? jg_await_verdict(role, fault, term_now, commit, jg_awt_u64(w1.x, w1.y), jg_awt_u64(w1.z, w1.w),
+                                             jg_awt_u64(w2.x, w2.y), a.now)
+                          : 0u;
+    if (in) a.verdict[i] = (uint8_t)v;
+    const uint64_t m = __ballot(in && v);
+    bc[0] += __popcll(__ballot(in && !v));
+    bc[1] += __popcll(m);
+    bc[2] += __popcll(__ballot(in && (v & JG_DONE_APPLIED)));
+    bc[3] += __popcll(__ballot(in && (v & JG_DONE_LOST)));
+    bc[4] += __popcll(__ballot(in && (v & JG_DONE_EXPIRED)));
+    if (lane == 0) wave_n[wave] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t t = 0;
+#pragma unroll
+      for (uint32_t x = 0; x < JG_BLOCK / 64; x++) t += wave_n[x];
+      a.bsum[tile] = t;
+    }
+    __syncthreads();  // (wave_n is the next tile's too)
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (uint32_t x = 0; x < JG_AWT_WORDS; x++) wave_b[wave][x] = bc[x];
+  }
+  __syncthreads();
+  if (threadIdx.x < JG_AWT_WORDS) {
+    uint64_t t = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < JG_BLOCK / 64; x++) t += wave_b[x][threadIdx.x];
+    a.part[(size_t)blockIdx.x * JG_AWT_WORDS + threadIdx.x] = t;
+  }
+}
+
+// one workgroup: wave x reduces words x, x + 4, ... over the partial records, its lanes side by side over the records
+__global__ __launch_bounds__(JG_BLOCK) void k_await_stats_sum(JgAwaitArgs a) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  for (uint32_t x = wave; x < JG_AWT_WORDS; x += JG_BLOCK / 64) {  // (uniform over the wave)
+    uint64_t t = 0;
+    for (uint32_t b = lane; b < a.parts; b += 64) t += a.part[(size_t)b * JG_AWT_WORDS + x];
+    t = jg_wave_sum64(t);
+    if (lane == 0) a.sum[x] = t;
+  }
+}
+
+__global__ __launch_bounds__(JG_BLOCK) void k_await_write(JgDev d, JgAwaitArgs a) {
+  __shared__ uint32_t wave_n[JG_BLOCK / 64];
+  const uint64_t total = *a.total;
+  if ((total < a.cap ? total : a.cap) == 0) return;  // (uniform over the launch) nothing is delivered: the table stays as it is
+  const uint64_t base = a.bsum[blockIdx.x];
+  if (a.peek && base >= a.cap) return;  // (uniform over the workgroup) a peek copies no waiter: wholly beyond cap
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t i = blockIdx.x * JG_AWT_TILE + threadIdx.x;
+  const bool in = i < a.n;
+  const uint32_t v = in ? a.verdict[i] : 0u;
+  const uint64_t m = __ballot(in && v);
+  if (lane == 0) wave_n[wave] = __popcll(m);
+  __syncthreads();
+  uint32_t before = 0;
+#pragma unroll
+  for (uint32_t x = 0; x < JG_BLOCK / 64; x++) before += x < wave ? wave_n[x] : 0u;
+  const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull;  // the lanes below this one
+  const uint64_t rank = base + before + __popcll(m & below);     // the done waiters before this one
+  if (!in) return;
+  const bool deliver = v && rank < a.cap;
+  if (!deliver && a.peek) return;
+  const size_t at = (size_t)i * 3;
+  const uint4 w0 = a.tab[at], w1 = a.tab[at + 1], w2 = a.tab[at + 2];
+  if (!deliver) {  // a survivor: behind it min(rank, cap) waiters leave
+    const size_t to = ((size_t)i - (size_t)(rank < a.cap ? rank : a.cap)) * 3;
+    a.dst[to] = w0, a.dst[to + 1] = w1, a.dst[to + 2] = w2;
+    return;
+  }
+  const uint32_t g = w0.x < d.G ? w0.x : 0u;
+  const uint32_t f = d.flags[g];
+  const uint64_t term_now = d.term[g], head = d.head[g];
+  const uint64_t commit = jg_read_commit(d, g, f);
+  const uint32_t role = f & JGF_ROLE_MASK, fault = (f & JGF_FAULT_MASK) >> JGF_FAULT_SHIFT, self = (f & JGF_SELF_MASK) >> JGF_SELF_SHIFT;
+  auto lo = [](uint64_t x) { return (uint32_t)x; };
+  auto hi = [](uint64_t x) { return (uint32_t)(x >> 32); };
+  // the row as three 16-byte pieces: {group, state | role | fault | self_slot, token} {block_id, term_now} {commit_now, head_now}
+  jg_u32x4* out = (jg_u32x4*)a.out + rank * 3;
+  out[0] = jg_u32x4{a.add + g, v | role << 8 | fault << 16 | self << 24, w0.z, w0.w};
+  out[1] = jg_u32x4{w1.x, w1.y, lo(term_now), hi(term_now)};
+  out[2] = jg_u32x4{lo(commit), hi(commit), lo(head), hi(head)};
+}

@@ -34,6 +34,7 @@
 #include "jg_isr_clock.h"
 #include "jg_lookup.h"
 #include "jg_commits.h"
+#include "jg_await.h"
 #include "jg_poll.h"
 
 // The host side, by entry-point family (ONE translation unit: the pieces see each other's internals, in this order)
@@ -54,4 +55,5 @@
 #include "jg_api_isr_clock.h"
 #include "jg_api_lookup.h"
 #include "jg_api_commits.h"
+#include "jg_api_await.h"
 #include "jg_api_poll.h"

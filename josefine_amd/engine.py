@@ -848,6 +848,53 @@ class BatchedRaft(_Hosting):
             return rows, int(total.value)
         return rows, int(total.value), {name: int(getattr(b, name)) for name, _ in capi.CommitBacklog._fields_}
 
+    def _await_api(self, name: str):
+        if not hasattr(self.api, name):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}{name}")
+        return getattr(self.api, name)
+
+    def open_waiters(self, capacity: int) -> None:
+        """jg_engine_await_open: (re)size the completion feed's table to `capacity` waiters (per shard on a multi-device
+        handle); 0 frees it.  Refused while waiters are outstanding."""
+        self._check(self._await_api("engine_await_open")(self._h, int(capacity)))
+
+    def await_blocks(self, groups, block_ids, tokens, terms=0, deadlines_ms=0) -> int:
+        """jg_engine_await_blocks: register one waiter per entry - (group, block id, token), guarded by `terms` where
+        nonzero, expiring at `deadlines_ms` where nonzero; scalars broadcast.  All or nothing.  Returns the number
+        registered."""
+        fn = self._await_api("engine_await_blocks")
+        groups = np.atleast_1d(np.asarray(groups))
+        rows = np.zeros(len(groups), capi.AWAIT_ROW_DTYPE)
+        if len(groups) and (groups.min() < 0 or groups.max() > 0xFFFFFFFF):
+            raise EngineError(capi.EINVAL, "await_blocks: group out of range")
+        rows["group"] = groups
+        for name, v in (("block_id", block_ids), ("token", tokens), ("term", terms), ("deadline_ms", deadlines_ms)):
+            rows[name] = np.asarray(v, dtype=np.uint64)
+        self._check(fn(self._h, rows.ctypes.data, len(rows)))
+        self._await_n = getattr(self, "_await_n", 0) + len(rows)
+        return len(rows)
+
+    def watch_completions(self, now_ms: int = 0, limit: Optional[int] = None, peek: bool = False, stats: bool = False):
+        """jg_engine_watch_completions: the waiters that are done at `now_ms` - applied, lost or expired, the verdict in
+        `state` (capi.DONE_*) - in registration order: (rows, total) with rows a structured array (capi.DONE_ROW_DTYPE) of
+        the first `limit` of them and total their number; with `stats` (rows, total, stats) with the fields of
+        jg_await_stats as a dict.  The delivered waiters leave the table; `peek` delivers the same rows and removes
+        nothing."""
+        fn = self._await_api("engine_watch_completions")
+        have = getattr(self, "_await_n", 0)
+        cap = have if limit is None else max(0, min(int(limit), have))
+        out = np.zeros(max(cap, 1), capi.DONE_ROW_DTYPE)
+        total = C.c_size_t(0)
+        s = capi.AwaitStats()
+        self._check(fn(self._h, capi.WATCH_PEEK if peek else 0, int(now_ms), out.ctypes.data, cap, C.byref(total),
+                       C.byref(s) if stats else None))
+        rows = out[:min(cap, total.value)]
+        if not peek:
+            self._await_n = have - len(rows)
+        if not stats:
+            return rows, int(total.value)
+        return rows, int(total.value), {name: int(getattr(s, name)) for name, _ in capi.AwaitStats._fields_}
+
     def _poll_request(self, leaders=None, replicas=None, commits=None, census: bool = False, repl_census: Optional[int] = None,
                       g0: int = 0, n: Optional[int] = None):
         """the jg_poll of `poll`'s arguments: (p, what it points at - to be kept alive over the call, {"backlog": asked for})"""

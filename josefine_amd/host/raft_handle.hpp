@@ -387,6 +387,27 @@ class BatchedRaft {
     if (total) *total = tot;
     return out;
   }
+  // The completion feed (jg_engine_await_open / _await_blocks / _watch_completions, ABI v22; only callers need a library
+  // that has it): fsm::Driver's notifications (fsm.rs:35) as a table of waiters on the device.  open_waiters (re)sizes the
+  // table (refused while waiters are outstanding; 0 frees it); await_blocks registers waiters, all or nothing;
+  // watch_completions returns the waiters that are done at now_ms - applied, lost or expired: jg_done_row.state - in
+  // registration order, at most `limit` rows, *total (if given) how many are done, *stats (if given) the counts before the
+  // delivery and what is left.  The delivered waiters leave the table unless `peek`.
+  void open_waiters(size_t capacity) { check(jg_engine_await_open(e_, capacity)); }
+  void await_blocks(const std::vector<jg_await_row>& rows) { check(jg_engine_await_blocks(e_, rows.data(), rows.size())); }
+  std::vector<jg_done_row> watch_completions(uint64_t now_ms = 0, size_t limit = SIZE_MAX, bool peek = false, size_t* total = nullptr,
+                                             jg_await_stats* stats = nullptr) {
+    size_t tot = 0;
+    if (limit == SIZE_MAX) {  // everything that is done: sized by a count
+      check(jg_engine_watch_completions(e_, JG_WATCH_PEEK, now_ms, nullptr, 0, &tot, nullptr));
+      limit = tot;
+    }
+    std::vector<jg_done_row> out(limit);
+    check(jg_engine_watch_completions(e_, peek ? (uint32_t)JG_WATCH_PEEK : 0u, now_ms, out.data(), out.size(), &tot, stats));
+    out.resize(std::min<size_t>(tot, out.size()));
+    if (total) *total = tot;
+    return out;
+  }
   // One poll per tick (jg_engine_poll, ABI v18; only callers need a library that has it): the parts `want` names of
   // watch_leaders, watch_replicas, watch_commits, census and replication_census over [g0, g0 + n) in ONE call - one settle,
   // one device pass over the slots, one synchronisation - each exactly as its own call answers it, the shadows shared with
