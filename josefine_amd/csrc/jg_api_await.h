@@ -1,8 +1,9 @@
 // jg_api_await.h - jg_engine_await_open / jg_engine_await_blocks / jg_engine_watch_completions: the completion feed
-// (jg_await.h).  Calls that read, under the rules of jg_api_manage.h and in the shape of jg_api_commits.h: refused while
-// kept node steps are outstanding, JG_NODE_ASYNC steps settled, the rows' landing area carved from the engine's staging, a
-// multi-device handle served shard by shard.  A watch queues its passes back to back and synchronises once; a registration
-// is one host-to-device copy behind the table's end.  Part of josefine_gpu.hip's one translation unit.
+// (jg_await.h).  Calls that read, under the rules of jg_api_manage.h: refused while kept node steps are outstanding,
+// JG_NODE_ASYNC steps settled, the rows' landing area carved from the engine's staging, a multi-device handle served shard
+// by shard.  A watch queues its passes back to back and synchronises once; a registration is one host-to-device copy
+// behind the table's end.  The feed walks a table, not a slot range, so it keeps a chain of its own (await_shard) beside
+// the other feeds' one host path (jg_api_poll.h).  Part of josefine_gpu.hip's one translation unit.
 #pragma once
 
 namespace {
@@ -195,11 +196,8 @@ int jg_engine_watch_completions(jg_engine* e, uint32_t flags, uint64_t now_ms, j
   }
   *total = at[D];
   if (sw) {
-    for (uint32_t x = 0; x < JG_AWT_WORDS; x++) {
-      uint64_t t = 0;
-      for (size_t d = 0; d < D; d++) t += w[d * JG_AWT_WORDS + x];
-      sw[x] = t;
-    }
+    std::memset(sw, 0, JG_AWT_WORDS * 8);
+    for (size_t d = 0; d < D; d++) merge_words(sw, w.data() + d * JG_AWT_WORDS, JG_AWT_WORDS, summed);
     sw[JG_AWT_WORDS] = left();
   }
   return JG_OK;

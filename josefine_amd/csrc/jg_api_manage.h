@@ -120,6 +120,13 @@ inline ShardPart shard_part(const jg_engine* e, size_t d, uint32_t g0, uint32_t 
   return {a - lo[d], b - a, a - g0};
 }
 
+// one shard's W gauge words merged into the handle's: summed, or the larger of the two where is_max(x) says so
+template <class IsMax>
+void merge_words(uint64_t* dst, const uint64_t* src, uint32_t W, IsMax is_max) {
+  for (uint32_t x = 0; x < W; x++) dst[x] = is_max(x) ? std::max(dst[x], src[x]) : dst[x] + src[x];
+}
+inline bool summed(uint32_t) { return false; }  // (an is_max for words that are all sums)
+
 // ---- refuse first, check, then write -----------------------------------------------------------------------------------
 
 // what refuses a call that rewrites group state before anything is touched (kept_refuse is what refuses one that reads it)

@@ -1,9 +1,12 @@
-// jg_api_poll.h - jg_engine_poll: the three change feeds and the two censuses of one tick in one call (jg_poll.h).  A call
-// that reads, under the rules of jg_api_manage.h and in the shape of jg_api_commits.h: every argument of every wanted part
-// checked before anything is queued, refused while kept node steps are outstanding, JG_NODE_ASYNC steps settled ONCE, one
-// block of scratch carved from the engine's staging for all parts, ONE count pass, one scan launch, the feeds' own write
-// passes and the census kernels queued back to back, the small answers copied asynchronously, ONE synchronisation, then
-// the rows of the feeds that have any.  A multi-device handle is served shard by shard.  And jg_step_node_polled /
+// jg_api_poll.h - the host path of the three change feeds and the two censuses (jg_watch.h, jg_isr.h, jg_isr_clock.h,
+// jg_commits.h, jg_poll.h), and jg_engine_poll: any subset of them for one tick in one call.  The separate calls
+// (jg_api_feeds.h) are the same path with one part wanted.  A call that reads, under the rules of jg_api_manage.h: every
+// argument of every wanted part checked before anything is queued, refused while kept node steps are outstanding (the
+// entry point's part), then poll_handle: JG_NODE_ASYNC steps settled ONCE, only the wanted feeds' shadows and clocks
+// allocated, one block of scratch carved from the engine's staging for all parts, ONE count pass (a single feed's own
+// kernel, else the fused one), one scan launch, the feeds' own write passes and the census kernels queued back to back,
+// the small answers copied asynchronously, ONE synchronisation, then the rows of the feeds that have any.  A multi-device
+// handle is served shard by shard: sized, then delivered.  And jg_step_node_polled /
 // jg_node_poll_view (ABI v21): the same chain queued BEHIND a kept node step over scratch of the step's own arena, gated on
 // the device by the step's general-row count, its header and rows sent home on the step's trip and handed out when the
 // step's outbox is viewed (node_poll_tail, node_poll_finish: called by jg_api_node.h).  Part of josefine_gpu.hip's one
@@ -61,16 +64,16 @@ int poll_plan(jg_engine* e, const PollShard& q, PollPlan& P, bool header) {
   for (int x = 0; x < 3; x++) P.on[x] = (q.want & POLL_BIT[x]) != 0;
   P.census = (q.want & JG_POLL_CENSUS) != 0, P.repl = (q.want & JG_POLL_REPL_CENSUS) != 0;
   P.backlog = P.on[POLL_C] && q.backlog;
-  if (P.on[POLL_L] && !e->watch_shadow)
+  if (P.on[POLL_L] && !e->watch_shadow)  // (zero: every slot was last reported vacant)
     if (const int rc = dev_alloc(e, &e->watch_shadow, e->cfg.n_groups)) return rc;
-  if (P.on[POLL_I] && !e->isr_shadow)
+  if (P.on[POLL_I] && !e->isr_shadow)  // (zero: no slot was last reported leading)
     if (const int rc = dev_alloc(e, &e->isr_shadow, e->cfg.n_groups)) return rc;
   P.timed = P.on[POLL_I] && q.timed;
-  if (P.timed && !e->isr_stamp)  // (the clocks, as isr_clock_shard allocates them: no member was behind at the last sample)
+  if (P.timed && !e->isr_stamp)  // (the clocks, zero-filled: no member was behind at the last sample)
     if (const int rc = dev_alloc(e, &e->isr_stamp, (size_t)e->cfg.n_replicas * e->cfg.n_groups)) return rc;
   if (P.timed && !e->isr_behind)
     if (const int rc = dev_alloc(e, &e->isr_behind, e->cfg.n_groups)) return rc;
-  if (P.on[POLL_C] && !e->commit_shadow)
+  if (P.on[POLL_C] && !e->commit_shadow)  // (zero: every slot was last delivered at genesis)
     if (const int rc = dev_alloc(e, &e->commit_shadow, e->cfg.n_groups)) return rc;
   JgPollArgs& a = P.a;
   a.tiles = (q.n + JG_POLL_TILE - 1) / JG_POLL_TILE;
@@ -371,55 +374,52 @@ int poll_check(const jg_engine* e, const jg_poll* p, bool outputs) {
   return JG_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int jg_engine_poll(jg_engine* e, jg_poll* p) {
-  if (!e || !p) return fail(JG_EINVAL, "null argument");
-  if (const int rc = poll_check(e, p, true)) return rc;
-  const bool on[3] = {(p->want & JG_POLL_LEADERS) != 0, (p->want & JG_POLL_REPLICAS) != 0, (p->want & JG_POLL_COMMITS) != 0};
-  const bool timed = on[POLL_I] && p->clock;
-  const jg_isr_clock clk = timed ? *p->clock : jg_isr_clock{};
-  if (const int rc = refuse_first(e, kept_refuse)) return rc;
-  const uint32_t fl[3] = {p->leader_flags, p->replica_flags, p->commit_flags};
-  void* const out[3] = {p->leaders, p->replicas, p->commits};
-  const size_t cap[3] = {p->leaders_cap, p->replicas_cap, p->commits_cap};
-  const bool backlog = on[POLL_C] && p->backlog;
-  // what every shard is asked, before its range, its rows and its caps
-  PollShard base;
-  base.want = p->want;
-  for (int x = 0; x < 3; x++) base.peek[x] = (fl[x] & JG_WATCH_PEEK) != 0;
-  base.commits_only = (p->commit_flags & JG_WATCH_COMMITS_ONLY) != 0;
-  base.pol = p->policy, base.lag_limit = p->census_lag_limit;
-  base.timed = timed, base.clk = clk;
-  const size_t D = shard_count(e);
-  std::vector<PollShard> q(D, base);
-  std::vector<uint64_t> w(D * JG_CMT_WORDS, 0);
-  std::vector<size_t> at[3];
-  if (!e->router) {  // (straight into the caller's arrays; the totals and the gauges only once the call has succeeded)
-    PollShard& s = q[0];
-    s.g0 = p->g0, s.n = p->n;
+// The ONE host path of every watch and census call, behind the caller's own checks and refuse_first: the parts `base` wants
+// (want, peeks, rules; its range, rows and caps are filled in here per shard) of the handle's slots [g0, g0 + n).  Per
+// wanted feed x the first cap[x] changed rows into out[x] and the number of differing slots into *total[x]; `backlog`
+// (null: not wanted), `census` and `repl` are the gauges' words.  The caller's totals and gauges are written only once the
+// whole call has succeeded.
+int poll_handle(jg_engine* e, const PollShard& base, uint32_t g0, uint32_t n, void* const out[3], const size_t cap[3], size_t* const total[3],
+                uint64_t* backlog, uint64_t* census, uint64_t* repl) {
+  const bool on[3] = {(base.want & JG_POLL_LEADERS) != 0, (base.want & JG_POLL_REPLICAS) != 0, (base.want & JG_POLL_COMMITS) != 0};
+  if (!on[POLL_C]) backlog = nullptr;
+  size_t tot[3] = {0, 0, 0};
+  uint64_t bw[JG_CMT_WORDS] = {}, cw[JG_CENSUS_WORDS] = {}, rw[JG_RC_WORDS] = {};
+  auto fold = [&](const PollShard& s) {  // a shard's sizes and gauges into the handle's
+    for (int x = 0; x < 3; x++) tot[x] += s.total[x];
+    if (s.backlog) merge_words(bw, s.backlog, JG_CMT_WORDS, summed);
+    merge_words(cw, s.census, JG_CENSUS_WORDS, [](uint32_t x) { return x == JG_CENSUS_MAX_TERM; });
+    merge_words(rw, s.repl, JG_RC_WORDS, [](uint32_t x) { return jg_rc_is_max(x); });
+  };
+  if (!e->router) {  // (straight into the caller's arrays, and nothing on the heap: a quiet call is all host overhead)
+    uint64_t w[JG_CMT_WORDS];
+    PollShard s = base;
+    s.g0 = g0, s.n = n;
     for (int x = 0; x < 3; x++) s.out[x] = out[x], s.cap[x] = cap[x];
-    s.backlog = backlog ? w.data() : nullptr;
+    s.backlog = backlog ? w : nullptr;
     if (const int rc = poll_shard(e, s)) return rc;
-    for (int x = 0; x < 3; x++) at[x] = {0, s.total[x]};
+    fold(s);
   } else {
     // a sharded handle: every shard is sized first by ONE fused peek that delivers nothing (the backlog and the censuses
     // are the shards' sums or maxima from that pass); then each shard delivers - and advances - into what is left of EACH
-    // feed's own cap behind the shards before it; a shard behind the point where a feed's cap ran out keeps that shadow.
+    // feed's own cap behind the shards before it; a shard behind the point where a feed's cap ran out keeps that shadow and,
+    // with no feed left to deliver, is not called again.
     // Under the time rule the sizing pass keeps the CALLER's peek for the replicas - it delivers nothing (cap 0) and, unless
     // the caller peeks, advances that shard's clocks: time passes on every shard, those behind the cap too; the delivering
     // pass advances them again at the same now_ms, which stores nothing
+    const size_t D = shard_count(e);
+    std::vector<PollShard> q(D, base);
+    std::vector<uint64_t> w(D * JG_CMT_WORDS, 0);
     int rc = each_shard(e, [&](size_t d) -> int {
-      const ShardPart sp = shard_part(e, d, p->g0, p->n);
+      const ShardPart sp = shard_part(e, d, g0, n);
       PollShard& s = q[d];
       s.g0 = sp.g0, s.n = sp.n;
-      for (int x = 0; x < 3; x++) s.peek[x] = x == POLL_I && timed ? base.peek[x] : true;
+      for (int x = 0; x < 3; x++) s.peek[x] = x == POLL_I && base.timed ? base.peek[x] : true;
       s.backlog = backlog ? w.data() + d * JG_CMT_WORDS : nullptr;
       return poll_shard(shard_at(e, d), s);
     });
     if (rc) return rc;
+    std::vector<size_t> at[3];  // where shard d's rows of feed x start among the handle's
     for (int x = 0; x < 3; x++) {
       at[x].assign(D + 1, 0);
       for (size_t d = 0; d < D; d++) at[x][d + 1] = at[x][d] + q[d].total[x];
@@ -437,35 +437,38 @@ int jg_engine_poll(jg_engine* e, jg_poll* p) {
       return poll_shard(shard_at(e, d), s);
     });
     if (rc) return rc;
+    for (const PollShard& s : q) fold(s);
   }
-  if (on[POLL_L]) p->leaders_total = at[POLL_L][D];
-  if (on[POLL_I]) p->replicas_total = at[POLL_I][D];
-  if (on[POLL_C]) p->commits_total = at[POLL_C][D];
-  if (backlog) {
-    uint64_t* bw = (uint64_t*)p->backlog;  // (jg_commit_backlog is the backlog words in order: jg_commits.h)
-    for (uint32_t x = 0; x < JG_CMT_WORDS; x++) {
-      uint64_t t = 0;
-      for (size_t d = 0; d < D; d++) t += w[d * JG_CMT_WORDS + x];
-      bw[x] = t;
-    }
-  }
-  if (p->want & JG_POLL_CENSUS) {
-    uint64_t* o = (uint64_t*)p->census;  // (jg_census is the census words in order: jg_watch.h)
-    for (uint32_t x = 0; x < JG_CENSUS_WORDS; x++) {
-      uint64_t t = 0;
-      for (size_t d = 0; d < D; d++) t = x == JG_CENSUS_MAX_TERM ? std::max(t, q[d].census[x]) : t + q[d].census[x];
-      o[x] = t;
-    }
-  }
-  if (p->want & JG_POLL_REPL_CENSUS) {
-    uint64_t* o = (uint64_t*)p->repl_census;  // (jg_repl_census is the census words in order: jg_isr.h)
-    for (uint32_t x = 0; x < JG_RC_WORDS; x++) {
-      uint64_t t = 0;
-      for (size_t d = 0; d < D; d++) t = jg_rc_is_max(x) ? std::max(t, q[d].repl[x]) : t + q[d].repl[x];
-      o[x] = t;
-    }
-  }
+  for (int x = 0; x < 3; x++)
+    if (on[x]) *total[x] = tot[x];
+  if (backlog) std::memcpy(backlog, bw, sizeof bw);
+  if (base.want & JG_POLL_CENSUS) std::memcpy(census, cw, sizeof cw);
+  if (base.want & JG_POLL_REPL_CENSUS) std::memcpy(repl, rw, sizeof rw);
   return JG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int jg_engine_poll(jg_engine* e, jg_poll* p) {
+  if (!e || !p) return fail(JG_EINVAL, "null argument");
+  if (const int rc = poll_check(e, p, true)) return rc;
+  if (const int rc = refuse_first(e, kept_refuse)) return rc;
+  const bool on[3] = {(p->want & JG_POLL_LEADERS) != 0, (p->want & JG_POLL_REPLICAS) != 0, (p->want & JG_POLL_COMMITS) != 0};
+  const uint32_t fl[3] = {p->leader_flags, p->replica_flags, p->commit_flags};
+  PollShard base;
+  base.want = p->want;
+  for (int x = 0; x < 3; x++) base.peek[x] = (fl[x] & JG_WATCH_PEEK) != 0;
+  base.commits_only = (p->commit_flags & JG_WATCH_COMMITS_ONLY) != 0;
+  base.pol = p->policy, base.lag_limit = p->census_lag_limit;
+  base.timed = on[POLL_I] && p->clock;  // (the clock of a replicas part that is not wanted is not dereferenced)
+  if (base.timed) base.clk = *p->clock;
+  void* const out[3] = {p->leaders, p->replicas, p->commits};
+  const size_t cap[3] = {p->leaders_cap, p->replicas_cap, p->commits_cap};
+  size_t* const total[3] = {&p->leaders_total, &p->replicas_total, &p->commits_total};
+  // (jg_commit_backlog, jg_census and jg_repl_census are their words in order: jg_commits.h, jg_watch.h, jg_isr.h)
+  return poll_handle(e, base, p->g0, p->n, out, cap, total, (uint64_t*)p->backlog, (uint64_t*)p->census, (uint64_t*)p->repl_census);
 }
 
 int jg_step_node_polled(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_poll* request) {

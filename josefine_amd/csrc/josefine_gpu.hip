@@ -50,10 +50,7 @@
 #include "jg_api_read.h"
 #include "jg_api_move.h"
 #include "jg_api_hosting.h"
-#include "jg_api_watch.h"
-#include "jg_api_isr.h"
-#include "jg_api_isr_clock.h"
 #include "jg_api_lookup.h"
-#include "jg_api_commits.h"
 #include "jg_api_await.h"
 #include "jg_api_poll.h"
+#include "jg_api_feeds.h"

@@ -541,6 +541,56 @@ def test_small_launches():
         assert (la, lb) == (10, 6), (what, la, lb)
 
 
+# The six separate calls are served by the poll's host path; what each queues is pinned here, per call, as the numbers the
+# calls had when each had a chain of its own.  One device: a count pass, the scan and - with a cap - the write pass; a
+# backlog is one launch more; a census is two.  Two shards: every shard is sized (no write pass), then the shards that have
+# rows within the cap deliver - a limit that ends inside shard 0 leaves shard 1 uncalled the second time.
+SEPARATE_LAUNCHES = {
+    1: dict(leaders=(2, 3, 3, 3), replicas=(2, 3, 3, 3), timed=(2, 3, 3, 3), commits=(2, 3, 3, 3), commits_backlog=(3, 4, 4, 4), census=2, repl_census=2),
+    2: dict(leaders=(4, 7, 10, 4), replicas=(4, 7, 10, 4), timed=(4, 7, 10, 4), commits=(4, 7, 10, 4), commits_backlog=(6, 9, 12, 6), census=4, repl_census=4),
+}
+
+
+@pytest.mark.parametrize("D", [pytest.param(1, id="small-one-device"), pytest.param(2, id="small-two-shards")])
+def test_launches_of_the_separate_calls(D):
+    G, R = 200, 3
+    inside = 50  # a limit that ends inside shard 0 (100 slots)
+
+    def engine():
+        e = BatchedRaft(G, R, seed=9, **(dict(device_ids=[0] * D) if D > 1 else {}))
+        busy((e,), G, R, wide_lag=False)
+        return e
+
+    def launched(e, call):
+        before = e.counters()["launches"]
+        r = call()
+        return e.counters()["launches"] - before, r
+
+    feeds = dict(
+        leaders=lambda e, **kw: e.watch_leaders(**kw),
+        replicas=lambda e, **kw: e.watch_replicas(2, 0, **kw),
+        timed=lambda e, **kw: e.watch_replicas_timed(5000, 100, **kw),
+        commits=lambda e, **kw: e.watch_commits(**kw),
+        commits_backlog=lambda e, **kw: e.watch_commits(backlog=True, **kw),
+    )
+    got = {}
+    for name, call in feeds.items():
+        e = engine()  # (a feed of its own engine: every slot is news to it)
+        assert D == 1 or e.shard(0).G > inside
+        ls = []
+        for what, kw, total in (("limit=0", dict(limit=0), G), ("a limit inside shard 0", dict(limit=inside), G), ("moved", {}, G - inside),
+                                ("quiet", {}, 0)):
+            k, r = launched(e, lambda: call(e, **kw))
+            assert r[1] == total and len(r[0]) == min(kw.get("limit", G), total), (name, what, r[1], len(r[0]))
+            ls.append(k)
+        got[name] = tuple(ls)
+    e = engine()
+    got["census"] = launched(e, e.census)[0]
+    got["repl_census"] = launched(e, lambda: e.replication_census(1))[0]
+    print("launches of the separate calls:", D, got)
+    assert got == SEPARATE_LAUNCHES[D], (D, got)
+
+
 # ---- 11. the stride (the device only) ----------------------------------------------------------------------------------------
 def test_the_stride():
     from josefine_amd.traces import elect_all
