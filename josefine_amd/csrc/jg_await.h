@@ -9,11 +9,12 @@
 //                      then its slot's columns as a gather in the manner of k_lookup - the flag word, term, head, mlag,
 //                      commit, run_hi, all issued before the first use (one round trip; 44 bytes used of six 64-byte
 //                      sectors) - the verdict byte stored, "done" counted by one 64-bit __ballot and a __popcll per wave,
-//                      the wave counts through LDS into the tile count.  A workgroup takes the tiles b, b + grid, ..., so
-//                      there are at most JG_AWT_PARTS partial stat records (counts by ballots: exact in any order)
+//                      the wave counts into the tile count (jg_tile_count, jg_compact.h).  A workgroup takes the tiles
+//                      b, b + grid, ..., so there are at most JG_AWT_PARTS partial stat records (jg_block_words; counts by
+//                      ballots: exact in any order)
 //   k_scan_block_sums  (jg_sparse.h) the tile counts -> exclusive prefixes and the total
-//   k_await_stats_sum  the partial records -> the stats (one workgroup)
-//   k_await_write      reads verdict and prefix: the rank among the done = ballot bits below + wave offset through LDS +
+//   k_await_stats_sum  the partial records -> the stats (jg_parts_reduce: one workgroup)
+//   k_await_write      reads verdict and prefix: the rank among the done = the rank in the tile (jg_rank_in_tile) + the
 //                      tile prefix.  Done and rank < cap: DELIVERED - the slot's columns gathered again (for delivered rows
 //                      only: the count pass keeps no side record) and the row written as three 16-byte stores.  Else,
 //                      unless peeking, the waiter is copied to position i - min(rank, cap) of the other buffer: one scan
@@ -27,7 +28,7 @@
 #include "jg_lookup.h"  // jg_u32x4
 #include "jg_read.h"    // jg_read_commit
 #include "jg_sparse.h"  // JgScanJob, k_scan_block_sums
-#include "jg_watch.h"   // jg_wave_sum64
+#include "jg_compact.h"
 
 #define JG_AWT_TILE JG_BLOCK  // waiters per tile of the passes: one lane per waiter
 // the most workgroups - partial stat records - of the count pass: four a CU on 256 CUs (JG_CMT_PARTS)
@@ -77,9 +78,6 @@ __device__ __forceinline__ uint32_t jg_await_verdict(uint32_t role, uint32_t fau
 }
 
 __global__ __launch_bounds__(JG_BLOCK) void k_await_count(JgDev d, JgAwaitArgs a) {
-  __shared__ uint32_t wave_n[JG_BLOCK / 64];
-  __shared__ uint64_t wave_b[JG_BLOCK / 64][JG_AWT_WORDS];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint32_t bc[JG_AWT_WORDS] = {0u, 0u, 0u, 0u, 0u};  // wave-uniform (every lane adds the same popcount)
   for (uint32_t tile = blockIdx.x; tile < a.tiles; tile += a.parts) {  // (uniform over the workgroup)
     const uint32_t i = tile * JG_AWT_TILE + threadIdx.x;
@@ -104,58 +102,27 @@ __global__ __launch_bounds__(JG_BLOCK) void k_await_count(JgDev d, JgAwaitArgs a
     bc[2] += __popcll(__ballot(in && (v & JG_DONE_APPLIED)));
     bc[3] += __popcll(__ballot(in && (v & JG_DONE_LOST)));
     bc[4] += __popcll(__ballot(in && (v & JG_DONE_EXPIRED)));
-    if (lane == 0) wave_n[wave] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t t = 0;
-#pragma unroll
-      for (uint32_t x = 0; x < JG_BLOCK / 64; x++) t += wave_n[x];
-      a.bsum[tile] = t;
-    }
-    __syncthreads();  // (wave_n is the next tile's too)
+    const uint32_t t = jg_tile_count(__popcll(m));
+    if (threadIdx.x == 0) a.bsum[tile] = t;
+    __syncthreads();  // (jg_tile_count's LDS is the next tile's too)
   }
-  if (lane == 0) {
-#pragma unroll
-    for (uint32_t x = 0; x < JG_AWT_WORDS; x++) wave_b[wave][x] = bc[x];
-  }
-  __syncthreads();
-  if (threadIdx.x < JG_AWT_WORDS) {
-    uint64_t t = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < JG_BLOCK / 64; x++) t += wave_b[x][threadIdx.x];
-    a.part[(size_t)blockIdx.x * JG_AWT_WORDS + threadIdx.x] = t;
-  }
+  const uint64_t vals[JG_AWT_WORDS] = {bc[0], bc[1], bc[2], bc[3], bc[4]};
+  jg_block_words<JG_AWT_WORDS>(vals, JgNeverMax(), a.part);
 }
 
-// one workgroup: wave x reduces words x, x + 4, ... over the partial records, its lanes side by side over the records
 __global__ __launch_bounds__(JG_BLOCK) void k_await_stats_sum(JgAwaitArgs a) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  for (uint32_t x = wave; x < JG_AWT_WORDS; x += JG_BLOCK / 64) {  // (uniform over the wave)
-    uint64_t t = 0;
-    for (uint32_t b = lane; b < a.parts; b += 64) t += a.part[(size_t)b * JG_AWT_WORDS + x];
-    t = jg_wave_sum64(t);
-    if (lane == 0) a.sum[x] = t;
-  }
+  jg_parts_reduce<JG_AWT_WORDS>(a.part, a.parts, a.sum, JgNeverMax());
 }
 
 __global__ __launch_bounds__(JG_BLOCK) void k_await_write(JgDev d, JgAwaitArgs a) {
-  __shared__ uint32_t wave_n[JG_BLOCK / 64];
   const uint64_t total = *a.total;
   if ((total < a.cap ? total : a.cap) == 0) return;  // (uniform over the launch) nothing is delivered: the table stays as it is
   const uint64_t base = a.bsum[blockIdx.x];
   if (a.peek && base >= a.cap) return;  // (uniform over the workgroup) a peek copies no waiter: wholly beyond cap
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t i = blockIdx.x * JG_AWT_TILE + threadIdx.x;
   const bool in = i < a.n;
   const uint32_t v = in ? a.verdict[i] : 0u;
-  const uint64_t m = __ballot(in && v);
-  if (lane == 0) wave_n[wave] = __popcll(m);
-  __syncthreads();
-  uint32_t before = 0;
-#pragma unroll
-  for (uint32_t x = 0; x < JG_BLOCK / 64; x++) before += x < wave ? wave_n[x] : 0u;
-  const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull;  // the lanes below this one
-  const uint64_t rank = base + before + __popcll(m & below);     // the done waiters before this one
+  const uint64_t rank = base + jg_rank_in_tile(__ballot(in && v));  // the done waiters before this one
   if (!in) return;
   const bool deliver = v && rank < a.cap;
   if (!deliver && a.peek) return;

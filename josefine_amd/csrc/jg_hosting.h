@@ -10,15 +10,15 @@
 //                    JG_CMD_RECREATE row does), the own slot first; returns at once when the error word is set
 //   k_groups_close   the write pass of a close: the canonical vacant record through jg_store plus the columns a follower's
 //                    jg_store leaves alone (packed progress, wide progress, window segments, foreign voters)
-//   k_list_count     stream compaction over the flag column, pass 1: per workgroup the number of matching slots (a 64-bit
-//                    __ballot and a __popcll per wave and row of 256 slots)
+//   k_list_count     stream compaction over the flag column (the skeleton of both passes: jg_compact.h), pass 1: per
+//                    workgroup the number of matching slots (a 64-bit __ballot and a __popcll per wave and row of 256 slots)
 //   k_scan_block_sums (jg_sparse.h) the workgroup counts -> exclusive prefixes and the total
-//   k_list_write     pass 2: the same ballots, the ranks within a wave from the ballot, the wave offsets through LDS; the
-//                    first `cap` matching indices ascending
+//   k_list_write     pass 2: the same ballots; the first `cap` matching indices ascending (jg_ranked_rows)
 //
 // The list, the own slots and a range's columns are read and written coalesced; a sparse list's column accesses are a
 // scatter (a memory transaction per 4- or 8-byte value) - a control-plane call, not a per-tick one.
 #pragma once
+#include "jg_compact.h"
 #include "jg_device.h"
 #include "jg_move.h"    // jg_move_deferred
 #include "jg_sparse.h"  // JgScanJob, k_scan_block_sums
@@ -151,46 +151,20 @@ __device__ __forceinline__ void jg_list_ballots(const JgDev& d, const JgListArgs
 }
 
 __global__ __launch_bounds__(JG_BLOCK) void k_list_count(JgDev d, JgListArgs a) {
-  __shared__ uint32_t wave_n[JG_BLOCK / 64];
   uint64_t m[JG_LIST_ROWS];
   jg_list_ballots(d, a, m);
   uint32_t c = 0;
 #pragma unroll
   for (uint32_t k = 0; k < JG_LIST_ROWS; k++) c += __popcll(m[k]);
-  if ((threadIdx.x & 63u) == 0) wave_n[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < JG_BLOCK / 64; w++) t += wave_n[w];
-    a.bsum[blockIdx.x] = t;
-  }
+  const uint32_t t = jg_tile_count(c);
+  if (threadIdx.x == 0) a.bsum[blockIdx.x] = t;
 }
 
 __global__ __launch_bounds__(JG_BLOCK) void k_list_write(JgDev d, JgListArgs a) {
-  __shared__ uint32_t wave_n[JG_LIST_ROWS][JG_BLOCK / 64];
-  uint64_t base = a.bsum[blockIdx.x];
+  const uint64_t base = a.bsum[blockIdx.x];
   if (base >= a.cap) return;  // (uniform over the workgroup) its matches are all beyond cap
   uint64_t m[JG_LIST_ROWS];
   jg_list_ballots(d, a, m);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (uint32_t k = 0; k < JG_LIST_ROWS; k++) wave_n[k][wave] = __popcll(m[k]);
-  }
-  __syncthreads();
-  const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull;  // the lanes below this one
   const uint32_t t0 = blockIdx.x * JG_LIST_TILE + threadIdx.x;
-#pragma unroll
-  for (uint32_t k = 0; k < JG_LIST_ROWS; k++) {
-    uint32_t before = 0, row = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < JG_BLOCK / 64; w++) {
-      before += w < wave ? wave_n[k][w] : 0u;
-      row += wave_n[k][w];
-    }
-    const uint64_t pos = base + before + __popcll(m[k] & below);
-    if (((m[k] >> lane) & 1ull) && pos < a.cap) a.out[pos] = a.add + a.g0 + t0 + k * JG_BLOCK;
-    base += row;
-  }
+  jg_ranked_rows<JG_LIST_ROWS>(m, base, a.cap, [&](uint32_t k, uint64_t pos) { a.out[pos] = a.add + a.g0 + t0 + k * JG_BLOCK; });
 }

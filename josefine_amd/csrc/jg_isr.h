@@ -9,25 +9,27 @@
 // engine's first watch; zero-filled it says "not leading, empty set".  Membership is hysteretic AGAINST the shadow: a member
 // the shadow holds stays while its lag is <= leave_lag, any other joins at lag <= join_lag.
 //
-//   k_isr_count        stream compaction over "view != shadow", pass 1: per workgroup the number of slots that differ (a
-//                      64-bit __ballot and a __popcll per wave and row of 256 slots); 16 bytes read per slot, the rare
-//                      fields (an escape, a base that is run_hi) decoded exactly under a branch
+//   k_isr_count        stream compaction over "view != shadow" (the skeleton of both passes: jg_compact.h), pass 1: per
+//                      workgroup the number of slots that differ (a 64-bit __ballot and a __popcll per wave and row of
+//                      256 slots); 16 bytes read per slot, the rare fields (an escape, a base that is run_hi) decoded
+//                      exactly under a branch
 //   k_scan_block_sums  (jg_sparse.h) the workgroup counts -> exclusive prefixes and the total
 //   k_isr_write        pass 2: a workgroup with nothing to report or wholly beyond `cap` returns after two loads; else the
-//                      same ballots, the head of the slots that differ, the ranks within a wave from the ballot, the wave
-//                      offsets through LDS; the first `cap` rows ascending as three 8-byte stores, and - unless peeking -
-//                      the shadow word of exactly those slots
+//                      same ballots and jg_isr_write_rows (k_isrc_write's too): the head of the slots that differ, the
+//                      first `cap` rows ascending as three 8-byte stores, and - unless peeking - the shadow word of
+//                      exactly those slots
 //   k_repl_census      one threshold, no shadow: the 1-bit predicates counted by ballots (one wave-uniform add per field
 //                      and row), the per-member lag maxima and sums and the largest head - commit by __shfl_down; a
 //                      workgroup strides over the tiles, so there are at most JG_REPL_CENSUS_PARTS partial records
-//   k_repl_census_sum  the partial records -> the census (one workgroup; no atomics anywhere)
+//                      (jg_block_words)
+//   k_repl_census_sum  the partial records -> the census (jg_parts_reduce: one workgroup; no atomics anywhere)
 //
 // Nothing here writes a column of the state machine: the only stores are the scratch, the rows and the shadow.
 #pragma once
 #include "jg_device.h"
 #include "jg_read.h"    // jg_read_commit
 #include "jg_sparse.h"  // JgScanJob, k_scan_block_sums
-#include "jg_watch.h"   // jg_wave_sum64, jg_wave_max64
+#include "jg_watch.h"   // jg_gated_peek (and jg_compact.h)
 
 #define JG_ISR_ROWS 4u  // rows of JG_BLOCK slots per workgroup of the watch passes (16 bytes in flight per lane and row)
 #define JG_ISR_TILE (JG_BLOCK * JG_ISR_ROWS)
@@ -134,8 +136,7 @@ struct JgIsrArgs {
 // flight per lane)
 __device__ __forceinline__ void jg_isr_ballots(const JgDev& d, const JgIsrArgs& a, uint32_t* v, uint32_t* f, uint64_t* w, uint64_t* m) {
   const uint32_t t0 = blockIdx.x * JG_ISR_TILE + threadIdx.x;
-  const uint32_t leave32 = a.leave_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.leave_lag;
-  const uint32_t join32 = a.join_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.join_lag;
+  const uint32_t leave32 = jg_clamp32(a.leave_lag), join32 = jg_clamp32(a.join_lag);
   uint32_t sh[JG_ISR_ROWS];
 #pragma unroll
   for (uint32_t k = 0; k < JG_ISR_ROWS; k++) {
@@ -156,76 +157,58 @@ __device__ __forceinline__ void jg_isr_ballots(const JgDev& d, const JgIsrArgs& 
 }
 
 __global__ __launch_bounds__(JG_BLOCK) void k_isr_count(JgDev d, JgIsrArgs a) {
-  __shared__ uint32_t wave_n[JG_BLOCK / 64];
   uint32_t v[JG_ISR_ROWS], f[JG_ISR_ROWS];
   uint64_t w[JG_ISR_ROWS], m[JG_ISR_ROWS];
   jg_isr_ballots(d, a, v, f, w, m);
   uint32_t c = 0;
 #pragma unroll
   for (uint32_t k = 0; k < JG_ISR_ROWS; k++) c += __popcll(m[k]);
-  if ((threadIdx.x & 63u) == 0) wave_n[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < JG_BLOCK / 64; x++) t += wave_n[x];
-    a.cnt[blockIdx.x] = t;
-    a.bsum[blockIdx.x] = t;
-  }
+  const uint32_t t = jg_tile_count(c);
+  if (threadIdx.x == 0) a.cnt[blockIdx.x] = t, a.bsum[blockIdx.x] = t;
 }
 
-__global__ __launch_bounds__(JG_BLOCK) void k_isr_write(JgDev d, JgIsrArgs a) {
-  __shared__ uint32_t wave_n[JG_ISR_ROWS][JG_BLOCK / 64];
-  uint64_t base = a.bsum[blockIdx.x];
-  // (uniform over the workgroup) nothing differs here - the quiet engine's every workgroup - or it is all beyond cap
-  if (a.cnt[blockIdx.x] == 0 || base >= a.cap) return;
-  uint32_t v[JG_ISR_ROWS], f[JG_ISR_ROWS];
-  uint64_t w[JG_ISR_ROWS], m[JG_ISR_ROWS];
-  jg_isr_ballots(d, a, v, f, w, m);
+// the write pass behind a feed's ballots (A: JgIsrArgs, or jg_isr_clock.h's JgIsrClockArgs): the rows of the slots of m
+// below a.cap from `base` (the tile's prefix) on, and - unless peeking - their shadow words
+template <class A>
+__device__ __forceinline__ void jg_isr_write_rows(const JgDev& d, const A& a, uint64_t base, const uint32_t* v, const uint32_t* f, const uint64_t* w,
+                                                  const uint64_t* m) {
   const uint32_t peek = jg_gated_peek(a.peek, a.gate);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t lane = threadIdx.x & 63u;
   const uint32_t t0 = blockIdx.x * JG_ISR_TILE + threadIdx.x;
   uint64_t head[JG_ISR_ROWS];
 #pragma unroll
   for (uint32_t k = 0; k < JG_ISR_ROWS; k++)  // the head of the slots that differ and lead: for their rows alone
     head[k] = (((m[k] >> lane) & 1ull) && v[k]) ? d.head[a.g0 + t0 + k * JG_BLOCK] : 0ull;
-  if (lane == 0) {
-#pragma unroll
-    for (uint32_t k = 0; k < JG_ISR_ROWS; k++) wave_n[k][wave] = __popcll(m[k]);
-  }
-  __syncthreads();
-  const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull;  // the lanes below this one
   const uint32_t R = d.R;
   uint64_t* out64 = (uint64_t*)a.out;
-#pragma unroll
-  for (uint32_t k = 0; k < JG_ISR_ROWS; k++) {
-    uint32_t before = 0, row = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < JG_BLOCK / 64; x++) {
-      before += x < wave ? wave_n[k][x] : 0u;
-      row += wave_n[k][x];
+  jg_ranked_rows<JG_ISR_ROWS>(m, base, a.cap, [&](uint32_t k, uint64_t pos) {
+    const uint32_t g = a.g0 + t0 + k * JG_BLOCK;
+    const uint32_t self = (f[k] & JGF_SELF_MASK) >> JGF_SELF_SHIFT;
+    uint32_t isr = 0, replicate = 0, state = 0;
+    uint64_t worst = 0;
+    if (v[k]) {
+      isr = v[k] & 0xffu;
+      const uint32_t in_sync = (uint32_t)__popcll((uint64_t)isr);
+      replicate = (f[k] & JGF_REPL_MASK) >> JGF_REPL_SHIFT;
+      state = JG_ISR_LEADS | (in_sync < R ? (uint32_t)JG_ISR_UNDER : 0u) | (in_sync < R / 2u + 1u ? (uint32_t)JG_ISR_BELOW_QUORUM : 0u);
+      worst = jg_isr_worst_lag(d, g, f[k], w[k], head[k]);
     }
-    const uint64_t pos = base + before + __popcll(m[k] & below);
-    if (((m[k] >> lane) & 1ull) && pos < a.cap) {
-      const uint32_t g = a.g0 + t0 + k * JG_BLOCK;
-      const uint32_t self = (f[k] & JGF_SELF_MASK) >> JGF_SELF_SHIFT;
-      uint32_t isr = 0, replicate = 0, state = 0;
-      uint64_t worst = 0;
-      if (v[k]) {
-        isr = v[k] & 0xffu;
-        const uint32_t in_sync = (uint32_t)__popcll((uint64_t)isr);
-        replicate = (f[k] & JGF_REPL_MASK) >> JGF_REPL_SHIFT;
-        state = JG_ISR_LEADS | (in_sync < R ? (uint32_t)JG_ISR_UNDER : 0u) | (in_sync < R / 2u + 1u ? (uint32_t)JG_ISR_BELOW_QUORUM : 0u);
-        worst = jg_isr_worst_lag(d, g, f[k], w[k], head[k]);
-      }
-      // the row as three 8-byte pieces: {group, isr, replicate, state, self_slot} {head} {worst_lag}
-      out64[pos * 3 + 0] = (uint64_t)(a.add + g) | (uint64_t)(isr | replicate << 8 | state << 16 | self << 24) << 32;
-      out64[pos * 3 + 1] = head[k];
-      out64[pos * 3 + 2] = worst;
-      if (!peek) a.shadow[g] = v[k];
-    }
-    base += row;
-  }
+    // the row as three 8-byte pieces: {group, isr, replicate, state, self_slot} {head} {worst_lag}
+    out64[pos * 3 + 0] = (uint64_t)(a.add + g) | (uint64_t)(isr | replicate << 8 | state << 16 | self << 24) << 32;
+    out64[pos * 3 + 1] = head[k];
+    out64[pos * 3 + 2] = worst;
+    if (!peek) a.shadow[g] = v[k];
+  });
+}
+
+__global__ __launch_bounds__(JG_BLOCK) void k_isr_write(JgDev d, JgIsrArgs a) {
+  const uint64_t base = a.bsum[blockIdx.x];
+  // (uniform over the workgroup) nothing differs here - the quiet engine's every workgroup - or it is all beyond cap
+  if (a.cnt[blockIdx.x] == 0 || base >= a.cap) return;
+  uint32_t v[JG_ISR_ROWS], f[JG_ISR_ROWS];
+  uint64_t w[JG_ISR_ROWS], m[JG_ISR_ROWS];
+  jg_isr_ballots(d, a, v, f, w, m);
+  jg_isr_write_rows(d, a, base, v, f, w, m);
 }
 
 struct JgReplCensusArgs {
@@ -238,7 +221,6 @@ struct JgReplCensusArgs {
 };
 
 __global__ __launch_bounds__(JG_BLOCK) void k_repl_census(JgDev d, JgReplCensusArgs a) {
-  __shared__ uint64_t wave_c[JG_BLOCK / 64][JG_RC_WORDS];
   const uint32_t R = d.R;
   uint32_t c[JG_RC_MAX_LAG];  // the counted fields: wave-uniform (every lane adds the same popcount)
 #pragma unroll
@@ -306,47 +288,18 @@ __global__ __launch_bounds__(JG_BLOCK) void k_repl_census(JgDev d, JgReplCensusA
       max_unc = unc > max_unc ? unc : max_unc;
     }
   }
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint64_t vals[JG_RC_WORDS];
+#pragma unroll
+  for (uint32_t x = 0; x < JG_RC_MAX_LAG; x++) vals[x] = c[x];
 #pragma unroll
   for (uint32_t r = 0; r < JG_MAX_REPLICAS; r++) {
-    max_lag[r] = jg_wave_max64(max_lag[r]);
-    sum_lag[r] = jg_wave_sum64(sum_lag[r]);
+    vals[JG_RC_MAX_LAG + r] = jg_wave_max64(max_lag[r]);
+    vals[JG_RC_SUM_LAG + r] = jg_wave_sum64(sum_lag[r]);
   }
-  max_unc = jg_wave_max64(max_unc);
-  if (lane == 0) {
-#pragma unroll
-    for (uint32_t x = 0; x < JG_RC_MAX_LAG; x++) wave_c[wave][x] = c[x];
-#pragma unroll
-    for (uint32_t r = 0; r < JG_MAX_REPLICAS; r++) {
-      wave_c[wave][JG_RC_MAX_LAG + r] = max_lag[r];
-      wave_c[wave][JG_RC_SUM_LAG + r] = sum_lag[r];
-    }
-    wave_c[wave][JG_RC_MAX_UNCOMMITTED] = max_unc;
-  }
-  __syncthreads();
-  if (threadIdx.x < JG_RC_WORDS) {
-    const bool is_max = jg_rc_is_max(threadIdx.x);
-    uint64_t t = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < JG_BLOCK / 64; x++) {
-      const uint64_t p = wave_c[x][threadIdx.x];
-      t = is_max ? (p > t ? p : t) : t + p;
-    }
-    a.part[(size_t)blockIdx.x * JG_RC_WORDS + threadIdx.x] = t;
-  }
+  vals[JG_RC_MAX_UNCOMMITTED] = jg_wave_max64(max_unc);
+  jg_block_words<JG_RC_WORDS>(vals, [](uint32_t x) { return jg_rc_is_max(x); }, a.part);
 }
 
-// one workgroup: wave x reduces words x, x + 4, ... over the partial records, its lanes side by side over the records
 __global__ __launch_bounds__(JG_BLOCK) void k_repl_census_sum(JgReplCensusArgs a) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  for (uint32_t x = wave; x < JG_RC_WORDS; x += JG_BLOCK / 64) {  // (uniform over the wave)
-    const bool is_max = jg_rc_is_max(x);
-    uint64_t t = 0;
-    for (uint32_t b = lane; b < a.parts; b += 64) {
-      const uint64_t p = a.part[(size_t)b * JG_RC_WORDS + x];
-      t = is_max ? (p > t ? p : t) : t + p;
-    }
-    t = is_max ? jg_wave_max64(t) : jg_wave_sum64(t);
-    if (lane == 0) a.out[x] = t;
-  }
+  jg_parts_reduce<JG_RC_WORDS>(a.part, a.parts, a.out, [](uint32_t x) { return jg_rc_is_max(x); });
 }

@@ -23,8 +23,9 @@
 //   k_scan_block_sums  (jg_sparse.h) the workgroup counts -> exclusive prefixes and the total
 //   k_isrc_write       pass 2: a workgroup with nothing to report or wholly beyond `cap` returns after two loads; else the
 //                      same view re-derived from the clocks already advanced (peeking: from the would-be clocks - the
-//                      same function of memory nobody wrote), the rows as k_isr_write writes them, and - unless peeking -
-//                      the shadow word of exactly the delivered slots.  It stores no clock
+//                      same function of memory nobody wrote), then jg_isr_write_rows (jg_isr.h): the rows as k_isr_write
+//                      writes them, and - unless peeking - the shadow word of exactly the delivered slots.  It stores no
+//                      clock
 //
 // A slot is one lane's from load to store in both passes; no atomics, no scratch.  Nothing here writes a column of the
 // state machine: the only stores are the scratch, the rows, the shadow and the clocks.
@@ -101,8 +102,7 @@ __device__ __forceinline__ uint32_t jg_isrc_word(const JgDev& d, const JgIsrCloc
 // four a row; a lane beyond n loads nothing)
 __device__ __forceinline__ void jg_isrc_ballots(const JgDev& d, const JgIsrClockArgs& a, bool advance, uint32_t* v, uint32_t* f, uint64_t* w, uint64_t* m) {
   const uint32_t t0 = blockIdx.x * JG_ISR_TILE + threadIdx.x;
-  const uint32_t caught32 = a.caught_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.caught_lag;
-  const uint32_t join32 = a.join_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.join_lag;
+  const uint32_t caught32 = jg_clamp32(a.caught_lag), join32 = jg_clamp32(a.join_lag);
   const uint32_t members_all = (1u << d.R) - 1u;  // (a mask byte never holds a bit at or above R: no stamp column there)
   uint32_t sh[JG_ISR_ROWS], mk[JG_ISR_ROWS];
 #pragma unroll
@@ -125,74 +125,22 @@ __device__ __forceinline__ void jg_isrc_ballots(const JgDev& d, const JgIsrClock
 }
 
 __global__ __launch_bounds__(JG_BLOCK) void k_isrc_count(JgDev d, JgIsrClockArgs a) {
-  __shared__ uint32_t wave_n[JG_BLOCK / 64];
   uint32_t v[JG_ISR_ROWS], f[JG_ISR_ROWS];
   uint64_t w[JG_ISR_ROWS], m[JG_ISR_ROWS];
   jg_isrc_ballots(d, a, !jg_gated_peek(a.peek, a.gate), v, f, w, m);
   uint32_t c = 0;
 #pragma unroll
   for (uint32_t k = 0; k < JG_ISR_ROWS; k++) c += __popcll(m[k]);
-  if ((threadIdx.x & 63u) == 0) wave_n[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < JG_BLOCK / 64; x++) t += wave_n[x];
-    a.cnt[blockIdx.x] = t;
-    a.bsum[blockIdx.x] = t;
-  }
+  const uint32_t t = jg_tile_count(c);
+  if (threadIdx.x == 0) a.cnt[blockIdx.x] = t, a.bsum[blockIdx.x] = t;
 }
 
 __global__ __launch_bounds__(JG_BLOCK) void k_isrc_write(JgDev d, JgIsrClockArgs a) {
-  __shared__ uint32_t wave_n[JG_ISR_ROWS][JG_BLOCK / 64];
-  uint64_t base = a.bsum[blockIdx.x];
+  const uint64_t base = a.bsum[blockIdx.x];
   // (uniform over the workgroup) nothing differs here - the quiet engine's every workgroup - or it is all beyond cap
   if (a.cnt[blockIdx.x] == 0 || base >= a.cap) return;
   uint32_t v[JG_ISR_ROWS], f[JG_ISR_ROWS];
   uint64_t w[JG_ISR_ROWS], m[JG_ISR_ROWS];
   jg_isrc_ballots(d, a, false, v, f, w, m);
-  const uint32_t peek = jg_gated_peek(a.peek, a.gate);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t t0 = blockIdx.x * JG_ISR_TILE + threadIdx.x;
-  uint64_t head[JG_ISR_ROWS];
-#pragma unroll
-  for (uint32_t k = 0; k < JG_ISR_ROWS; k++)  // the head of the slots that differ and lead: for their rows alone
-    head[k] = (((m[k] >> lane) & 1ull) && v[k]) ? d.head[a.g0 + t0 + k * JG_BLOCK] : 0ull;
-  if (lane == 0) {
-#pragma unroll
-    for (uint32_t k = 0; k < JG_ISR_ROWS; k++) wave_n[k][wave] = __popcll(m[k]);
-  }
-  __syncthreads();
-  const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull;  // the lanes below this one
-  const uint32_t R = d.R;
-  uint64_t* out64 = (uint64_t*)a.out;
-#pragma unroll
-  for (uint32_t k = 0; k < JG_ISR_ROWS; k++) {
-    uint32_t before = 0, row = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < JG_BLOCK / 64; x++) {
-      before += x < wave ? wave_n[k][x] : 0u;
-      row += wave_n[k][x];
-    }
-    const uint64_t pos = base + before + __popcll(m[k] & below);
-    if (((m[k] >> lane) & 1ull) && pos < a.cap) {
-      const uint32_t g = a.g0 + t0 + k * JG_BLOCK;
-      const uint32_t self = (f[k] & JGF_SELF_MASK) >> JGF_SELF_SHIFT;
-      uint32_t isr = 0, replicate = 0, state = 0;
-      uint64_t worst = 0;
-      if (v[k]) {
-        isr = v[k] & 0xffu;
-        const uint32_t in_sync = (uint32_t)__popcll((uint64_t)isr);
-        replicate = (f[k] & JGF_REPL_MASK) >> JGF_REPL_SHIFT;
-        state = JG_ISR_LEADS | (in_sync < R ? (uint32_t)JG_ISR_UNDER : 0u) | (in_sync < R / 2u + 1u ? (uint32_t)JG_ISR_BELOW_QUORUM : 0u);
-        worst = jg_isr_worst_lag(d, g, f[k], w[k], head[k]);
-      }
-      // the row as three 8-byte pieces: {group, isr, replicate, state, self_slot} {head} {worst_lag}
-      out64[pos * 3 + 0] = (uint64_t)(a.add + g) | (uint64_t)(isr | replicate << 8 | state << 16 | self << 24) << 32;
-      out64[pos * 3 + 1] = head[k];
-      out64[pos * 3 + 2] = worst;
-      if (!peek) a.shadow[g] = v[k];
-    }
-    base += row;
-  }
+  jg_isr_write_rows(d, a, base, v, f, w, m);
 }

@@ -4,9 +4,10 @@
 // A tick of an event loop that consumes several feeds asks "what changed leader, whose in-sync set changed, what was
 // committed or appended" of the same slots.  Asked separately the three count passes read 44 + 16 + 44 = 104 bytes per
 // slot; here the flag word and mlag are read once: 88 bytes where all three are wanted.  The views, the shadows and the
-// comparisons are the feeds' own - jg_lead_view, jg_isr_word, the commit decode of jg_commit_ballots - so the per-feed
-// cnt[tile] / bsum[tile] this pass writes are exactly what k_watch_write, k_isr_write and k_commit_write index, and the
-// commit backlog's partial records are what k_commit_backlog_sum adds up: those kernels run unchanged behind it.
+// comparisons are the feeds' own functions - jg_lead_view / jg_lead_differs, jg_isr_word, jg_commit_view /
+// jg_commit_differs / jg_commit_backlog_add - so the per-feed cnt[tile] / bsum[tile] this pass writes are exactly what
+// k_watch_write, k_isr_write and k_commit_write index, and the commit backlog's partial records are what
+// k_commit_backlog_sum adds up: those kernels run unchanged behind it.  The tails are jg_compact.h's.
 //
 //   k_poll_count<L, I, C>  the feeds wanted are launch-uniform template switches (two or three of them: a single feed has
 //                          its own count kernel); commits_only and backlog are launch-uniform words of the commit feed's
@@ -14,11 +15,12 @@
 //                          walks a tile of four rows as passes of JG_POLL_FLIGHT rows: every distinct column of the
 //                          wanted feeds loaded once, all of a pass's loads in flight before the first use; per feed and
 //                          row one __ballot and one __popcll per wave, both 32-bit halves of every compared word
-//   k_poll_count_timed<L, C>  the same walk with the replicas part under the TIME rule (jg_isr_clock.h; the part is implied,
-//                          and wanted alone it is k_isrc_count's): the mask byte joins the loads of a pass, the word is
-//                          jg_isrc_word as it stands - the stamp gathers and, unless peeking, the stores of the clocks
-//                          behind its own conditions - and no lag policy is read: 89 bytes where all three are wanted and no
-//                          clock runs.  Its cnt[tile] / bsum[tile] are what k_isrc_write indexes
+//   k_poll_count_timed<L, C>  the same body (jg_poll_count_body<L, true, C, true>) with the replicas part under the TIME
+//                          rule (jg_isr_clock.h; the part is implied, and wanted alone it is k_isrc_count's): the mask
+//                          byte joins the loads of a pass, the word is jg_isrc_word as it stands - the stamp gathers and,
+//                          unless peeking, the stores of the clocks behind its own conditions - and no lag policy is
+//                          read: 89 bytes where all three are wanted and no clock runs.  Its cnt[tile] / bsum[tile] are
+//                          what k_isrc_write indexes
 //   k_scan_block_sums      (jg_sparse.h) one launch, one workgroup per wanted feed's bsum array
 //   k_poll_header          (at the end of this file) a polled node step's answer but the rows as one block: one copy home
 //
@@ -56,13 +58,12 @@ struct JgPollArgs {
 // its shadow, wave-uniform; bc / commits / appends: the commit backlog as k_commit_count keeps it.  T: the replicas part is
 // under the time rule - leave32 is then caught_lag's 32-bit clamp, and with `advance` (the call does not peek and its gate
 // is shut: uniform over the launch) the clocks of the rows advance
-template <bool L, bool I, bool C, bool T = false>
+template <bool L, bool I, bool C, bool T>
 __device__ __forceinline__ void jg_poll_rows(const JgDev& d, const JgPollArgs& a, uint32_t g0, uint32_t n, uint32_t tile, uint32_t k0,
                                              uint32_t leave32, uint32_t join32, uint32_t lane, bool advance, uint32_t* c, uint32_t* bc,
                                              uint64_t& commits, uint64_t& appends) {
   static_assert(I || !T, "the time rule is the replicas part's");
   const uint32_t t0 = tile * JG_POLL_TILE + k0 * JG_BLOCK + threadIdx.x;
-  const uint32_t R = d.R;
   uint32_t f[JG_POLL_FLIGHT], ish[JG_POLL_FLIGHT], mk[JG_POLL_FLIGHT];
   uint64_t term[JG_POLL_FLIGHT], w[JG_POLL_FLIGHT], head[JG_POLL_FLIGHT], col[JG_POLL_FLIGHT];
   uint4 cold[JG_POLL_FLIGHT], lsh[JG_POLL_FLIGHT], csh[JG_POLL_FLIGHT];
@@ -79,7 +80,7 @@ __device__ __forceinline__ void jg_poll_rows(const JgDev& d, const JgPollArgs& a
     }
     if (I || C) w[k] = in ? d.mlag[g] : 0ull;
     if (I) ish[k] = in ? (T ? a.ic.shadow : a.ir.shadow)[g] : 0u;
-    if (T) mk[k] = in ? (uint32_t)a.ic.mask[g] & ((1u << R) - 1u) : 0u;  // (no bit at or above R: no stamp column there)
+    if (T) mk[k] = in ? (uint32_t)a.ic.mask[g] & ((1u << d.R) - 1u) : 0u;  // (no bit at or above R: no stamp column there)
     if (C) {
       head[k] = in ? d.head[g] : 0ull;
       col[k] = in ? d.commit[g] : 0ull;
@@ -100,12 +101,8 @@ __device__ __forceinline__ void jg_poll_rows(const JgDev& d, const JgPollArgs& a
   for (uint32_t k = 0; k < JG_POLL_FLIGHT; k++) {
     const uint32_t i = t0 + k * JG_BLOCK;
     const bool in = i < n;
-    if (L) {  // jg_watch_ballots
-      const JgLeadView v = jg_lead_view(d, f[k], term[k], cold[k].y);
-      const bool differs = lsh[k].x != (uint32_t)v.term || lsh[k].y != (uint32_t)(v.term >> 32) || lsh[k].z != v.leader_id ||
-                           lsh[k].w != (v.meta ^ JG_WATCH_VACANT_META);
-      c[0] += __popcll(__ballot(in && differs));
-    }
+    if (L)  // jg_watch_ballots
+      c[0] += __popcll(__ballot(in && jg_lead_differs(lsh[k], jg_lead_view(d, f[k], term[k], cold[k].y))));
     if (I && !T) {  // jg_isr_ballots
       const uint32_t v = in ? jg_isr_word(d, a.ir.leave_lag, a.ir.join_lag, leave32, join32, g0 + i, f[k], w[k], ish[k]) : 0u;
       c[1] += __popcll(__ballot(in && v != ish[k]));
@@ -115,128 +112,52 @@ __device__ __forceinline__ void jg_poll_rows(const JgDev& d, const JgPollArgs& a
       c[1] += __popcll(__ballot(in && v != ish[k]));
     }
     if (C) {  // jg_commit_ballots, and the backlog of k_commit_count
-      const bool leader = (f[k] & JGF_ROLE_MASK) == JG_ROLE_LEADER;
-      const uint64_t fc = jg_lag_field(w[k], R, R);
-      uint64_t cm = leader ? head[k] - fc : col[k];  // the common case: a leader's commit IS head - field
-      if (leader && (jg_lag_wide(fc, R) || jg_lag_base_is_run_hi(f[k]))) cm = jg_read_commit(d, g0 + (in ? i : 0u), f[k]);  // rare: exact
-      const bool differs = csh[k].x != (uint32_t)cm || csh[k].y != (uint32_t)(cm >> 32) ||
-                           (!a.cm.commits_only && (csh[k].z != (uint32_t)head[k] || csh[k].w != (uint32_t)(head[k] >> 32)));
-      const uint64_t m = __ballot(in && differs);
+      const uint64_t cm = jg_commit_view(d, g0 + (in ? i : 0u), f[k], w[k], head[k], col[k]);
+      const uint64_t m = __ballot(in && jg_commit_differs(csh[k], cm, head[k], a.cm.commits_only));
       c[2] += __popcll(m);
-      if (a.cm.backlog) {  // (uniform over the launch)
-        const bool on = (m >> lane) & 1ull;
-        const uint64_t cf = jg_cmt_u64(csh[k].x, csh[k].y), hf = jg_cmt_u64(csh[k].z, csh[k].w);
-        const bool up_c = on && cm > cf, up_h = on && head[k] > hf;
-        bc[0] += __popcll(m);
-        bc[1] += __popcll(__ballot(up_c));
-        bc[2] += __popcll(__ballot(up_h));
-        bc[3] += __popcll(__ballot(on && (cm < cf || head[k] < hf)));
-        commits += up_c ? cm - cf : 0ull;
-        appends += up_h ? head[k] - hf : 0ull;
-      }
+      if (a.cm.backlog) jg_commit_backlog_add((m >> lane) & 1ull, m, csh[k], cm, head[k], bc, commits, appends);  // (uniform over the launch)
     }
   }
 }
 
-template <bool L, bool I, bool C>
-__global__ __launch_bounds__(JG_BLOCK) void k_poll_count(JgDev d, JgPollArgs a) {
-  __shared__ uint32_t wave_n[3][JG_BLOCK / 64];
-  __shared__ uint64_t wave_b[JG_BLOCK / 64][JG_CMT_WORDS];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t g0 = L ? a.lw.g0 : a.ir.g0, n = L ? a.lw.n : a.ir.n;  // (two feeds at least: one of these is wanted)
-  const uint32_t leave32 = a.ir.leave_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.ir.leave_lag;
-  const uint32_t join32 = a.ir.join_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.ir.join_lag;
+// the count pass: T - the replicas part is under the time rule, its arguments a.ic in place of a.ir
+template <bool L, bool I, bool C, bool T>
+__device__ __forceinline__ void jg_poll_count_body(const JgDev& d, const JgPollArgs& a) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t g0 = T ? a.ic.g0 : L ? a.lw.g0 : a.ir.g0, n = T ? a.ic.n : L ? a.lw.n : a.ir.n;  // (two feeds at least: one of these is wanted)
+  const uint32_t leave32 = jg_clamp32(T ? a.ic.caught_lag : a.ir.leave_lag), join32 = jg_clamp32(T ? a.ic.join_lag : a.ir.join_lag);
+  const bool advance = T && !jg_gated_peek(a.ic.peek, a.ic.gate);  // (one scalar load per workgroup, outside the walk)
   uint32_t bc[4] = {0u, 0u, 0u, 0u};  // changed, committed, appended, rewound: wave-uniform
   uint64_t commits = 0, appends = 0;  // per lane
   for (uint32_t tile = blockIdx.x; tile < a.tiles; tile += a.parts) {  // (uniform over the workgroup)
     uint32_t c[3] = {0u, 0u, 0u};
 #pragma unroll
     for (uint32_t k0 = 0; k0 < JG_POLL_ROWS; k0 += JG_POLL_FLIGHT)
-      jg_poll_rows<L, I, C>(d, a, g0, n, tile, k0, leave32, join32, lane, false, c, bc, commits, appends);
-    if (lane == 0) {
-#pragma unroll
-      for (uint32_t x = 0; x < 3; x++) wave_n[x][wave] = c[x];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {  // thread x: feed x's count of the tile
+      jg_poll_rows<L, I, C, T>(d, a, g0, n, tile, k0, leave32, join32, lane, advance, c, bc, commits, appends);
+    const uint32_t t = jg_tile_counts<3>(c);
+    if (threadIdx.x < 3) {  // thread x: feed x's count of the tile (ONE guard: a branch per feed cost the pass 0.6 us at 1 M)
       const uint32_t x = threadIdx.x;
-      uint32_t t = 0;
-#pragma unroll
-      for (uint32_t y = 0; y < JG_BLOCK / 64; y++) t += wave_n[x][y];
       if (L && x == 0) a.lw.cnt[tile] = t, a.lw.bsum[tile] = t;
-      if (I && x == 1) a.ir.cnt[tile] = t, a.ir.bsum[tile] = t;
+      if (I && x == 1) (T ? a.ic.cnt : a.ir.cnt)[tile] = t, (T ? a.ic.bsum : a.ir.bsum)[tile] = t;
       if (C && x == 2) a.cm.cnt[tile] = t, a.cm.bsum[tile] = t;
     }
-    __syncthreads();  // (wave_n is the next tile's too)
+    __syncthreads();  // (jg_tile_counts' LDS is the next tile's too)
   }
   if (!C || !a.cm.backlog) return;
-  commits = jg_wave_sum64(commits);
-  appends = jg_wave_sum64(appends);
-  if (lane == 0) {
-#pragma unroll
-    for (uint32_t x = 0; x < 4; x++) wave_b[wave][x] = bc[x];
-    wave_b[wave][4] = commits;
-    wave_b[wave][5] = appends;
-  }
-  __syncthreads();
-  if (threadIdx.x < JG_CMT_WORDS) {
-    uint64_t t = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < JG_BLOCK / 64; x++) t += wave_b[x][threadIdx.x];
-    a.cm.part[(size_t)blockIdx.x * JG_CMT_WORDS + threadIdx.x] = t;
-  }
+  const uint64_t vals[JG_CMT_WORDS] = {bc[0], bc[1], bc[2], bc[3], jg_wave_sum64(commits), jg_wave_sum64(appends)};
+  jg_block_words<JG_CMT_WORDS>(vals, JgNeverMax(), a.cm.part);
+}
+
+template <bool L, bool I, bool C>
+__global__ __launch_bounds__(JG_BLOCK) void k_poll_count(JgDev d, JgPollArgs a) {
+  jg_poll_count_body<L, I, C, false>(d, a);
 }
 
 // k_poll_count's walk with the replicas part under the time rule: L / C the other feeds wanted (one of them at least)
 template <bool L, bool C>
 __global__ __launch_bounds__(JG_BLOCK) void k_poll_count_timed(JgDev d, JgPollArgs a) {
   static_assert(L || C, "a timed replicas part wanted alone is k_isrc_count's");
-  __shared__ uint32_t wave_n[3][JG_BLOCK / 64];
-  __shared__ uint64_t wave_b[JG_BLOCK / 64][JG_CMT_WORDS];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t g0 = a.ic.g0, n = a.ic.n;
-  const uint32_t caught32 = a.ic.caught_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.ic.caught_lag;
-  const uint32_t join32 = a.ic.join_lag > 0xffffffffull ? 0xffffffffu : (uint32_t)a.ic.join_lag;
-  const bool advance = !jg_gated_peek(a.ic.peek, a.ic.gate);  // (one scalar load per workgroup, outside the walk)
-  uint32_t bc[4] = {0u, 0u, 0u, 0u};  // changed, committed, appended, rewound: wave-uniform
-  uint64_t commits = 0, appends = 0;  // per lane
-  for (uint32_t tile = blockIdx.x; tile < a.tiles; tile += a.parts) {  // (uniform over the workgroup)
-    uint32_t c[3] = {0u, 0u, 0u};
-#pragma unroll
-    for (uint32_t k0 = 0; k0 < JG_POLL_ROWS; k0 += JG_POLL_FLIGHT)
-      jg_poll_rows<L, true, C, true>(d, a, g0, n, tile, k0, caught32, join32, lane, advance, c, bc, commits, appends);
-    if (lane == 0) {
-#pragma unroll
-      for (uint32_t x = 0; x < 3; x++) wave_n[x][wave] = c[x];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {  // thread x: feed x's count of the tile
-      const uint32_t x = threadIdx.x;
-      uint32_t t = 0;
-#pragma unroll
-      for (uint32_t y = 0; y < JG_BLOCK / 64; y++) t += wave_n[x][y];
-      if (L && x == 0) a.lw.cnt[tile] = t, a.lw.bsum[tile] = t;
-      if (x == 1) a.ic.cnt[tile] = t, a.ic.bsum[tile] = t;
-      if (C && x == 2) a.cm.cnt[tile] = t, a.cm.bsum[tile] = t;
-    }
-    __syncthreads();  // (wave_n is the next tile's too)
-  }
-  if (!C || !a.cm.backlog) return;
-  commits = jg_wave_sum64(commits);
-  appends = jg_wave_sum64(appends);
-  if (lane == 0) {
-#pragma unroll
-    for (uint32_t x = 0; x < 4; x++) wave_b[wave][x] = bc[x];
-    wave_b[wave][4] = commits;
-    wave_b[wave][5] = appends;
-  }
-  __syncthreads();
-  if (threadIdx.x < JG_CMT_WORDS) {
-    uint64_t t = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < JG_BLOCK / 64; x++) t += wave_b[x][threadIdx.x];
-    a.cm.part[(size_t)blockIdx.x * JG_CMT_WORDS + threadIdx.x] = t;
-  }
+  jg_poll_count_body<L, true, C, true>(d, a);
 }
 
 // ---- the header of a poll that travels with a node step (jg_step_node_polled) -------------------------------------------

@@ -6,18 +6,21 @@
 // engine's first watch.  The meta word is stored XOR the vacant view's, so the zero-filled allocation IS "every slot was
 // last reported vacant".
 //
-//   k_watch_count      stream compaction over "view != shadow", pass 1: per workgroup the number of slots that differ (a
-//                      64-bit __ballot and a __popcll per wave and row of 256 slots); 44 bytes read per slot
+//   k_watch_count      stream compaction over "view != shadow" (the skeleton of both passes: jg_compact.h), pass 1: per
+//                      workgroup the number of slots that differ (a 64-bit __ballot and a __popcll per wave and row of
+//                      256 slots); 44 bytes read per slot
 //   k_scan_block_sums  (jg_sparse.h) the workgroup counts -> exclusive prefixes and the total
 //   k_watch_write      pass 2: a workgroup with nothing to report or wholly beyond `cap` returns at once; else the same
-//                      ballots, the ranks within a wave from the ballot, the wave offsets through LDS; the first `cap`
-//                      rows ascending, and - unless peeking - the shadow of exactly those slots
+//                      ballots, the first `cap` rows ascending (jg_ranked_rows), and - unless peeking - the shadow of
+//                      exactly those slots
 //   k_census           one pass of 1-bit predicates counted by ballots (one wave-uniform add per field and row), the term
 //                      maximum and the leaders' head - commit by __shfl_down; one partial record per workgroup
-//   k_census_sum       the partial records -> the census (one workgroup; no atomics anywhere)
+//                      (jg_block_words)
+//   k_census_sum       the partial records -> the census (jg_parts_reduce: one workgroup; no atomics anywhere)
 //
 // Nothing here writes a column of the state machine: the only stores are the scratch, the rows and the shadow.
 #pragma once
+#include "jg_compact.h"
 #include "jg_device.h"
 #include "jg_hosting.h"  // jg_flags_vacant
 #include "jg_read.h"     // jg_read_commit
@@ -65,6 +68,13 @@ __device__ __forceinline__ JgLeadView jg_lead_view(const JgDev& d, uint32_t f, u
   v.meta = role | (state << 8) | (fault << 16);
   return v;
 }
+// the view as the shadow's 16 bytes, and "the shadow sh is not the view v"
+__device__ __forceinline__ uint4 jg_lead_shadow(const JgLeadView& v) {
+  return make_uint4((uint32_t)v.term, (uint32_t)(v.term >> 32), v.leader_id, v.meta ^ JG_WATCH_VACANT_META);
+}
+__device__ __forceinline__ bool jg_lead_differs(const uint4& sh, const JgLeadView& v) {
+  return sh.x != (uint32_t)v.term || sh.y != (uint32_t)(v.term >> 32) || sh.z != v.leader_id || sh.w != (v.meta ^ JG_WATCH_VACANT_META);
+}
 
 // the peek a pass acts on: the call's own, or the gate's verdict - ONE scalar load per workgroup (the pointer and the word are
 // uniform), taken behind the early return of a quiet workgroup, never inside the walk over the slots
@@ -102,14 +112,11 @@ __device__ __forceinline__ void jg_watch_ballots(const JgDev& d, const JgWatchAr
   for (uint32_t k = 0; k < JG_WATCH_ROWS; k++) {
     const uint32_t i = t0 + k * JG_BLOCK;
     v[k] = jg_lead_view(d, f[k], term[k], cold[k].y);
-    const bool differs = sh[k].x != (uint32_t)v[k].term || sh[k].y != (uint32_t)(v[k].term >> 32) || sh[k].z != v[k].leader_id ||
-                         sh[k].w != (v[k].meta ^ JG_WATCH_VACANT_META);
-    m[k] = __ballot(i < a.n && differs);
+    m[k] = __ballot(i < a.n && jg_lead_differs(sh[k], v[k]));
   }
 }
 
 __global__ __launch_bounds__(JG_BLOCK) void k_watch_count(JgDev d, JgWatchArgs a) {
-  __shared__ uint32_t wave_n[JG_BLOCK / 64];
   JgLeadView v[JG_WATCH_ROWS];
   uint32_t f[JG_WATCH_ROWS];
   uint64_t m[JG_WATCH_ROWS];
@@ -117,20 +124,12 @@ __global__ __launch_bounds__(JG_BLOCK) void k_watch_count(JgDev d, JgWatchArgs a
   uint32_t c = 0;
 #pragma unroll
   for (uint32_t k = 0; k < JG_WATCH_ROWS; k++) c += __popcll(m[k]);
-  if ((threadIdx.x & 63u) == 0) wave_n[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < JG_BLOCK / 64; w++) t += wave_n[w];
-    a.cnt[blockIdx.x] = t;
-    a.bsum[blockIdx.x] = t;
-  }
+  const uint32_t t = jg_tile_count(c);
+  if (threadIdx.x == 0) a.cnt[blockIdx.x] = t, a.bsum[blockIdx.x] = t;
 }
 
 __global__ __launch_bounds__(JG_BLOCK) void k_watch_write(JgDev d, JgWatchArgs a) {
-  __shared__ uint32_t wave_n[JG_WATCH_ROWS][JG_BLOCK / 64];
-  uint64_t base = a.bsum[blockIdx.x];
+  const uint64_t base = a.bsum[blockIdx.x];
   // (uniform over the workgroup) nothing differs here - the quiet engine's every workgroup - or it is all beyond cap
   if (a.cnt[blockIdx.x] == 0 || base >= a.cap) return;
   JgLeadView v[JG_WATCH_ROWS];
@@ -138,35 +137,17 @@ __global__ __launch_bounds__(JG_BLOCK) void k_watch_write(JgDev d, JgWatchArgs a
   uint64_t m[JG_WATCH_ROWS];
   jg_watch_ballots(d, a, v, f, m);
   const uint32_t peek = jg_gated_peek(a.peek, a.gate);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (uint32_t k = 0; k < JG_WATCH_ROWS; k++) wave_n[k][wave] = __popcll(m[k]);
-  }
-  __syncthreads();
-  const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull;  // the lanes below this one
   const uint32_t t0 = blockIdx.x * JG_WATCH_TILE + threadIdx.x;
   uint64_t* out64 = (uint64_t*)a.out;
-#pragma unroll
-  for (uint32_t k = 0; k < JG_WATCH_ROWS; k++) {
-    uint32_t before = 0, row = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < JG_BLOCK / 64; w++) {
-      before += w < wave ? wave_n[k][w] : 0u;
-      row += wave_n[k][w];
-    }
-    const uint64_t pos = base + before + __popcll(m[k] & below);
-    if (((m[k] >> lane) & 1ull) && pos < a.cap) {
-      const uint32_t g = a.g0 + t0 + k * JG_BLOCK;
-      const uint32_t self = (f[k] & JGF_SELF_MASK) >> JGF_SELF_SHIFT;
-      // the row as three 8-byte pieces: {group, leader_id} {term} {role, state, fault, self_slot, reserved}
-      out64[pos * 3 + 0] = (uint64_t)(a.add + g) | (uint64_t)v[k].leader_id << 32;
-      out64[pos * 3 + 1] = v[k].term;
-      out64[pos * 3 + 2] = (uint64_t)(v[k].meta | self << 24);
-      if (!peek) a.shadow[g] = make_uint4((uint32_t)v[k].term, (uint32_t)(v[k].term >> 32), v[k].leader_id, v[k].meta ^ JG_WATCH_VACANT_META);
-    }
-    base += row;
-  }
+  jg_ranked_rows<JG_WATCH_ROWS>(m, base, a.cap, [&](uint32_t k, uint64_t pos) {
+    const uint32_t g = a.g0 + t0 + k * JG_BLOCK;
+    const uint32_t self = (f[k] & JGF_SELF_MASK) >> JGF_SELF_SHIFT;
+    // the row as three 8-byte pieces: {group, leader_id} {term} {role, state, fault, self_slot, reserved}
+    out64[pos * 3 + 0] = (uint64_t)(a.add + g) | (uint64_t)v[k].leader_id << 32;
+    out64[pos * 3 + 1] = v[k].term;
+    out64[pos * 3 + 2] = (uint64_t)(v[k].meta | self << 24);
+    if (!peek) a.shadow[g] = jg_lead_shadow(v[k]);
+  });
 }
 
 struct JgCensusArgs {
@@ -177,22 +158,7 @@ struct JgCensusArgs {
   uint64_t* out;    // [JG_CENSUS_WORDS]
 };
 
-__device__ __forceinline__ uint64_t jg_wave_sum64(uint64_t v) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // (lane 0 holds the sum)
-}
-__device__ __forceinline__ uint64_t jg_wave_max64(uint64_t v) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) {
-    const uint64_t o = __shfl_down(v, off, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(JG_BLOCK) void k_census(JgDev d, JgCensusArgs a) {
-  __shared__ uint64_t wave_c[JG_BLOCK / 64][JG_CENSUS_WORDS];
   const uint32_t t0 = blockIdx.x * JG_CENSUS_TILE + threadIdx.x;
   uint32_t c[JG_CENSUS_MAX_TERM];  // the counted fields: wave-uniform (every lane adds the same popcount)
 #pragma unroll
@@ -240,38 +206,14 @@ __global__ __launch_bounds__(JG_BLOCK) void k_census(JgDev d, JgCensusArgs a) {
       if (healthy && role == JG_ROLE_LEADER) uncommitted += d.head[g] - jg_read_commit(d, g, f[k]);
     }
   }
-  max_term = jg_wave_max64(max_term);
-  uncommitted = jg_wave_sum64(uncommitted);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (lane == 0) {
+  uint64_t vals[JG_CENSUS_WORDS];
 #pragma unroll
-    for (uint32_t x = 0; x < JG_CENSUS_MAX_TERM; x++) wave_c[wave][x] = c[x];
-    wave_c[wave][JG_CENSUS_MAX_TERM] = max_term;
-    wave_c[wave][JG_CENSUS_UNCOMMITTED] = uncommitted;
-  }
-  __syncthreads();
-  if (threadIdx.x < JG_CENSUS_WORDS) {
-    uint64_t t = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < JG_BLOCK / 64; w++) {
-      const uint64_t x = wave_c[w][threadIdx.x];
-      t = threadIdx.x == JG_CENSUS_MAX_TERM ? (x > t ? x : t) : t + x;
-    }
-    a.part[(size_t)blockIdx.x * JG_CENSUS_WORDS + threadIdx.x] = t;
-  }
+  for (uint32_t x = 0; x < JG_CENSUS_MAX_TERM; x++) vals[x] = c[x];
+  vals[JG_CENSUS_MAX_TERM] = jg_wave_max64(max_term);
+  vals[JG_CENSUS_UNCOMMITTED] = jg_wave_sum64(uncommitted);
+  jg_block_words<JG_CENSUS_WORDS>(vals, [](uint32_t x) { return x == JG_CENSUS_MAX_TERM; }, a.part);
 }
 
-// one workgroup: wave w reduces words w, w + 4, ... over the partial records, its lanes side by side over the records
 __global__ __launch_bounds__(JG_BLOCK) void k_census_sum(JgCensusArgs a) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  for (uint32_t x = wave; x < JG_CENSUS_WORDS; x += JG_BLOCK / 64) {  // (uniform over the wave)
-    const bool is_max = x == JG_CENSUS_MAX_TERM;
-    uint64_t t = 0;
-    for (uint32_t b = lane; b < a.tiles; b += 64) {
-      const uint64_t p = a.part[(size_t)b * JG_CENSUS_WORDS + x];
-      t = is_max ? (p > t ? p : t) : t + p;
-    }
-    t = is_max ? jg_wave_max64(t) : jg_wave_sum64(t);
-    if (lane == 0) a.out[x] = t;
-  }
+  jg_parts_reduce<JG_CENSUS_WORDS>(a.part, a.tiles, a.out, [](uint32_t x) { return x == JG_CENSUS_MAX_TERM; });
 }

@@ -28,6 +28,7 @@
 #include "jg_load.h"
 #include "jg_read.h"
 #include "jg_move.h"
+#include "jg_compact.h"
 #include "jg_hosting.h"
 #include "jg_watch.h"
 #include "jg_isr.h"
