@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 22u /* v22: jg_engine_await_open / jg_engine_await_blocks / jg_engine_watch_completions (the completion feed: fsm::Driver's notifications on the device); v21: jg_step_node_polled / jg_node_poll_view (a poll behind a kept node step: the feeds with two ticks in flight); v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 23u /* v23: jg_step_node_awaited / jg_node_await_view (completions behind a kept node step: the purgatory with two ticks in flight); v22: jg_engine_await_open / jg_engine_await_blocks / jg_engine_watch_completions (the completion feed: fsm::Driver's notifications on the device); v21: jg_step_node_polled / jg_node_poll_view (a poll behind a kept node step: the feeds with two ticks in flight); v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -1263,6 +1263,54 @@ typedef struct jg_node_poll {
 } jg_node_poll;
 int jg_step_node_polled(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_poll* request);
 int jg_node_poll_view(jg_engine* e, jg_node_poll* out);
+
+/* ---- completions behind a kept node step (ABI v23) ------------------------------------------------
+ * The completion feed's three calls are refused while kept steps are outstanding, like every feed's.
+ * An AWAITED step carries a registration and a watch with it, as a polled step carries its poll.
+ *
+ * CONTRACT.  Let S be the engine after kept step t is settled and before anything else touches it.  The
+ * answer viewed for step t is what jg_engine_await_blocks(e, rows, n) and then
+ * jg_engine_watch_completions(e, flags, now_ms, out, cap, &total, &stats) leave when called on S: every
+ * row byte, total, all six stat words; and the table afterwards holds the same waiters in the same order.
+ * Consecutive awaited steps are consecutive register-then-watch pairs: what a small cap leaves pending at
+ * step t is pending at step t + 1.  A kept step without the attachment leaves the table alone.  The
+ * three synchronous calls stay refused while kept steps are outstanding; once none is they may be mixed
+ * with awaited steps on one engine - there is one table.
+ *
+ * jg_step_node_awaited with await == NULL is exactly jg_step_node_polled(e, now_ms, flags, poll).
+ * Otherwise the polled step's rules hold (JG_NODE_ASYNC | JG_NODE_KEEP, no multi-device parent), *await
+ * and its rows are copied at entry, and every argument is checked by the rules of jg_engine_await_blocks
+ * and jg_engine_watch_completions - and `poll`, if not NULL, by jg_engine_poll's - before anything of the
+ * step is queued: a refused call steps nothing and leaves the submitted rows queued.  The poll, if both
+ * are attached, is queued first.
+ *
+ * CAPACITY.  With steps outstanding the host does not know how many waiters the table holds; it keeps a
+ * BOUND: the waiters outstanding as of the newest viewed step or synchronous call, plus every row
+ * registered by steps begun since then.  bound + n > capacity: JG_ECAPACITY, nothing is stepped.  (What
+ * an outstanding step's watch removes lowers the bound when that step is viewed, not before.)
+ *
+ * jg_node_await_view answers for the kept step whose outbox jg_node_outbox_view finished last; JG_EINVAL
+ * if no kept step has been viewed yet.  attached == 0: that step carried no request (JG_OK, everything
+ * else 0).  The rows live in the set's pinned landing area and stay valid as long as that view's outbox
+ * columns do.  state: JG_NODE_POLL_REDONE as for the poll - the step had general-path rows, the chain
+ * behind its first pass touched nothing (the device saw the count) and ran behind the catch-up pass. */
+typedef struct jg_node_await_request {
+  const jg_await_row* rows;           /* [n] registered first; n == 0: watch only                          */
+  size_t n;
+  uint32_t flags;                     /* 0 or JG_WATCH_PEEK                                                 */
+  uint32_t want_stats;                /* 0 / 1                                                              */
+  uint64_t now_ms;                    /* != UINT64_MAX                                                      */
+  size_t cap;                         /* rows the caller takes; 0: counts only                              */
+} jg_node_await_request;
+int jg_step_node_awaited(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_poll* poll /* may be NULL */,
+                         const jg_node_await_request* await /* may be NULL */);
+typedef struct jg_node_await {
+  uint32_t attached, state;           /* 1: the step carried a request; JG_NODE_POLL_REDONE                 */
+  const jg_done_row* rows;            /* [rows_n], registration order; rows_n = min(cap, total)             */
+  size_t rows_n, total;
+  jg_await_stats stats;               /* zero unless wanted                                                 */
+} jg_node_await;
+int jg_node_await_view(jg_engine* e, jg_node_await* out);
 
 /* ---- a closed loop of dense node ticks ------------------------------------------------------------
  * All R nodes of every partition in ONE process (one engine per node, e.g. the three brokers of

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -288,6 +288,18 @@ class NodePoll(C.Structure):
                 ("backlog", CommitBacklog), ("census", Census), ("repl_census", ReplCensus)]
 
 
+class NodeAwaitRequest(C.Structure):
+    """jg_node_await_request."""
+    _fields_ = [("rows", C.c_void_p), ("n", C.c_size_t), ("flags", C.c_uint32), ("want_stats", C.c_uint32), ("now_ms", C.c_uint64),
+                ("cap", C.c_size_t)]
+
+
+class NodeAwait(C.Structure):
+    """jg_node_await."""
+    _fields_ = [("attached", C.c_uint32), ("state", C.c_uint32), ("rows", C.c_void_p), ("rows_n", C.c_size_t), ("total", C.c_size_t),
+                ("stats", AwaitStats)]
+
+
 # mailbox words (josefine_gpu.h: JG_ANSWER / JG_AE)
 MAILBOX_NONE = (1 << 56) - 1
 
@@ -435,6 +447,8 @@ class Api:
         "engine_poll": (C.c_int, [_P, C.POINTER(Poll)]),
         "step_node_polled": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.POINTER(Poll)]),
         "node_poll_view": (C.c_int, [_P, C.POINTER(NodePoll)]),
+        "step_node_awaited": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.POINTER(Poll), C.POINTER(NodeAwaitRequest)]),
+        "node_await_view": (C.c_int, [_P, C.POINTER(NodeAwait)]),
     }
     # only the oracle has these
     _ORACLE_PROTOS = {
@@ -486,4 +500,5 @@ HEADER_SYMBOLS = [
     "jg_step_node_polled", "jg_node_poll_view",
     "jg_engine_watch_replicas_timed",
     "jg_engine_await_open", "jg_engine_await_blocks", "jg_engine_watch_completions",
+    "jg_step_node_awaited", "jg_node_await_view",
 ]

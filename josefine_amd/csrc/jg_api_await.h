@@ -3,14 +3,19 @@
 // JG_NODE_ASYNC steps settled, the rows' landing area carved from the engine's staging, a multi-device handle served shard
 // by shard.  A watch queues its passes back to back and synchronises once; a registration is one host-to-device copy
 // behind the table's end.  The feed walks a table, not a slot range, so it keeps a chain of its own (await_shard) beside
-// the other feeds' one host path (jg_api_poll.h).  Part of josefine_gpu.hip's one translation unit.
+// the other feeds' one host path (jg_api_poll.h), in the same three pieces: await_plan hands out the geometry and the
+// sections of one block, await_bind the arguments over whoever's block it is, await_queue the chain.  The synchronous watch
+// is those pieces over the engine's staging with the host's n and cur; an AWAITED node step (jg_step_node_awaited, ABI v23:
+// node_await_stage / node_await_tail / node_await_finish, called by jg_api_node.h) is the same pieces over a block of the
+// kept-step set's arena with the table's head read on the device.  Part of josefine_gpu.hip's one translation unit.
 #pragma once
 
 namespace {
 
 // offsets in AwaitTable::misc
-constexpr size_t AWT_O_TOTAL = 0, AWT_O_SUM = 16, AWT_O_JOB = 64, AWT_MISC_BYTES = 128;
-static_assert(AWT_O_SUM + JG_AWT_WORDS * 8 <= AWT_O_JOB && AWT_O_JOB + sizeof(JgScanJob) <= AWT_MISC_BYTES, "AwaitTable::misc");
+constexpr size_t AWT_O_TOTAL = 0, AWT_O_SUM = 16, AWT_O_JOB = 64, AWT_O_HEAD = 128, AWT_MISC_BYTES = 144;
+static_assert(AWT_O_SUM + JG_AWT_WORDS * 8 <= AWT_O_JOB && AWT_O_JOB + sizeof(JgScanJob) <= AWT_O_HEAD, "AwaitTable::misc");
+static_assert(AWT_O_HEAD % 16 == 0 && AWT_O_HEAD + sizeof(JgAwaitHead) <= AWT_MISC_BYTES, "AwaitTable::misc: the head");
 // (a waiter's index, and the tile count, are 32-bit in the kernels)
 constexpr size_t AWT_MAX_CAPACITY = 0xFFFF0000ull;
 
@@ -51,6 +56,87 @@ int await_append_shard(jg_engine* e, const jg_await_row* rows, size_t n) {
   return JG_OK;
 }
 
+// One watch's chain of kernels over ONE block of scratch (the rows' landing area; an awaited step's staged rows and header
+// block too): the table's own buffers, verdict bytes, tile counts and partial records serve both.  `kept`: the chain of an
+// awaited node step - the head is the device's, n is the host's bound on it.
+struct AwaitPlan {
+  bool kept = false;
+  uint32_t n = 0, tiles = 0, parts = 0;  // the waiters the passes are launched for
+  size_t m = 0, wcap = 0;                // staged rows (kept); rows the landing area holds
+  Carve c;
+  size_t o_out = 0, o_rows = 0, o_hdr = 0;
+  JgAwaitArgs a{};
+  JgAwaitKeptArgs k{};
+};
+
+void await_plan(AwaitPlan& P, bool kept, size_t n, size_t m, size_t cap) {
+  P.kept = kept, P.n = (uint32_t)n, P.m = m;
+  P.tiles = std::max<uint32_t>((P.n + JG_AWT_TILE - 1) / JG_AWT_TILE, kept ? 1u : 0u);  // (an awaited step's header wants its total: one tile at least)
+  P.parts = std::min<uint32_t>(P.tiles, JG_AWT_PARTS);
+  P.wcap = std::min<size_t>(cap, n);
+  P.o_out = P.c.sect(P.wcap * sizeof(jg_done_row));
+  if (kept) P.o_rows = P.c.sect(m * sizeof(jg_await_row)), P.o_hdr = P.c.sect(JG_AH_WORDS * 8);
+}
+
+// the arguments of every pass over block B; `gate`: null, or the device word that makes an awaited step's chain leave
+// everything alone (jg_await.h)
+void await_bind(jg_engine* e, AwaitPlan& P, char* B, bool peek, bool stats, uint64_t now_ms, uint32_t add, const uint32_t* gate) {
+  jg_engine::AwaitTable& t = e->await;
+  if (!P.kept) {
+    JgAwaitArgs& a = P.a;
+    a.n = P.n, a.add = add, a.peek = peek ? 1u : 0u, a.tiles = P.tiles, a.parts = P.parts, a.now = now_ms, a.cap = P.wcap;
+    a.tab = t.buf[t.cur], a.dst = t.buf[t.cur ^ 1], a.verdict = t.verdict;
+    a.bsum = t.bsum, a.part = t.part;
+    a.sum = (uint64_t*)(t.misc + AWT_O_SUM), a.total = (const uint64_t*)(t.misc + AWT_O_TOTAL);
+    a.out = (uint4*)(B + P.o_out);
+    return;
+  }
+  JgAwaitKeptArgs& k = P.k;
+  k.m = (uint32_t)P.m, k.room = (uint32_t)t.cap, k.peek = peek ? 1u : 0u, k.tiles = P.tiles, k.parts = P.parts, k.stats = stats ? 1u : 0u;
+  k.now = now_ms, k.cap = P.wcap;
+  k.head = (JgAwaitHead*)(t.misc + AWT_O_HEAD), k.gate = gate;
+  k.rows = (const uint4*)(B + P.o_rows), k.buf[0] = t.buf[0], k.buf[1] = t.buf[1], k.verdict = t.verdict;
+  k.bsum = t.bsum, k.part = t.part, k.total = (const uint64_t*)(t.misc + AWT_O_TOTAL);
+  k.out = (uint4*)(B + P.o_out), k.hdr = (uint64_t*)(B + P.o_hdr);
+}
+
+// the whole chain on the engine's stream (`job`: where the device reads the scan job): [the append,] the count pass, the
+// scan, the stats sum if wanted, the write pass - queued unseen: with nothing done every workgroup returns after its first
+// loads - [and the header kernel, which folds the stats itself]
+int await_queue(jg_engine* e, const AwaitPlan& P, const JgScanJob* job, bool stats) {
+  jg_engine::AwaitTable& t = e->await;
+  const dim3 block(JG_BLOCK);
+  uint64_t* const total = (uint64_t*)(t.misc + AWT_O_TOTAL);
+  if (!P.kept) {
+    hipLaunchKernelGGL(k_await_count, dim3(P.parts), block, 0, e->stream, e->dev, P.a);
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), block, 0, e->stream, job, total);
+    e->n_launch += 2;
+    if (stats) {
+      hipLaunchKernelGGL(k_await_stats_sum, dim3(1), block, 0, e->stream, P.a);
+      e->n_launch++;
+    }
+    if (P.wcap) {
+      hipLaunchKernelGGL(k_await_write, dim3(P.tiles), block, 0, e->stream, e->dev, P.a);
+      e->n_launch++;
+    }
+  } else {
+    if (P.m) {
+      hipLaunchKernelGGL(k_await_append, dim3((uint32_t)((P.m * 3 + JG_BLOCK - 1) / JG_BLOCK)), block, 0, e->stream, P.k);
+      e->n_launch++;
+    }
+    hipLaunchKernelGGL(k_await_count_kept, dim3(P.parts), block, 0, e->stream, e->dev, P.k);
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), block, 0, e->stream, job, total);
+    if (P.wcap) {
+      hipLaunchKernelGGL(k_await_write_kept, dim3(P.tiles), block, 0, e->stream, e->dev, P.k);
+      e->n_launch++;
+    }
+    hipLaunchKernelGGL(k_await_header, dim3(1), block, 0, e->stream, P.k);
+    e->n_launch += 3;
+  }
+  HIPCHK(hipGetLastError());
+  return JG_OK;
+}
+
 // one single-device engine's part of a completion watch: the first `cap` done waiters (groups + add) into host `out`,
 // removed unless peeking; *total the done waiters; w (if not null) [JG_AWT_WORDS] the stats before the delivery
 int await_shard(jg_engine* e, uint32_t flags, uint64_t now_ms, uint32_t add, jg_done_row* out, size_t cap, size_t* total, uint64_t* w) {
@@ -63,43 +149,139 @@ int await_shard(jg_engine* e, uint32_t flags, uint64_t now_ms, uint32_t add, jg_
   }
   jg_engine::AwaitTable& t = e->await;
   if (!t.n) return JG_OK;
-  JgAwaitArgs a{};
-  a.n = (uint32_t)t.n, a.add = add, a.peek = (flags & JG_WATCH_PEEK) ? 1u : 0u;
-  a.tiles = (a.n + JG_AWT_TILE - 1) / JG_AWT_TILE;
-  a.parts = std::min<uint32_t>(a.tiles, JG_AWT_PARTS);
-  a.now = now_ms;
-  const size_t wcap = std::min<size_t>(cap, t.n);
-  Carve c;
-  const size_t o_out = c.sect(wcap * sizeof(jg_done_row));
+  const bool peek = (flags & JG_WATCH_PEEK) != 0;
+  AwaitPlan P;
+  await_plan(P, false, t.n, 0, cap);
   char* B = nullptr;
-  if (const int rc = c.on_staging(e, B)) return rc;
-  a.cap = wcap;
-  a.tab = t.buf[t.cur], a.dst = t.buf[t.cur ^ 1], a.verdict = t.verdict;
-  a.bsum = t.bsum, a.part = t.part;
-  a.sum = (uint64_t*)(t.misc + AWT_O_SUM), a.total = (const uint64_t*)(t.misc + AWT_O_TOTAL);
-  a.out = (uint4*)(B + o_out);
-  const JgScanJob job{a.bsum, a.tiles, 0};
+  if (const int rc = P.c.on_staging(e, B)) return rc;
+  await_bind(e, P, B, peek, w != nullptr, now_ms, add, nullptr);
+  const JgScanJob job{t.bsum, P.tiles, 0};
   HIPCHK(hipMemcpyAsync(t.misc + AWT_O_JOB, &job, sizeof job, hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(k_await_count, dim3(a.parts), dim3(JG_BLOCK), 0, e->stream, e->dev, a);
-  hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(JG_BLOCK), 0, e->stream, (const JgScanJob*)(t.misc + AWT_O_JOB), (uint64_t*)(t.misc + AWT_O_TOTAL));
-  e->n_launch += 2;
-  if (w) {
-    hipLaunchKernelGGL(k_await_stats_sum, dim3(1), dim3(JG_BLOCK), 0, e->stream, a);
-    e->n_launch++;
-  }
-  if (wcap) {  // (queued unseen: with nothing done every workgroup returns after its first load)
-    hipLaunchKernelGGL(k_await_write, dim3(a.tiles), dim3(JG_BLOCK), 0, e->stream, e->dev, a);
-    e->n_launch++;
-  }
-  HIPCHK(hipGetLastError());
+  if (const int rc = await_queue(e, P, (const JgScanJob*)(t.misc + AWT_O_JOB), w != nullptr)) return rc;
   uint64_t tot = 0;
   HIPCHK(hipMemcpyAsync(&tot, t.misc + AWT_O_TOTAL, 8, hipMemcpyDeviceToHost, e->stream));
-  if (w) HIPCHK(hipMemcpyAsync(w, a.sum, JG_AWT_WORDS * 8, hipMemcpyDeviceToHost, e->stream));
+  if (w) HIPCHK(hipMemcpyAsync(w, P.a.sum, JG_AWT_WORDS * 8, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   *total = (size_t)tot;
-  const size_t k = std::min<size_t>(wcap, tot);
-  if (k) HIPCHK(hipMemcpy(out, a.out, k * sizeof(jg_done_row), hipMemcpyDeviceToHost));
-  if (k && !a.peek) t.cur ^= 1, t.n -= k;  // the survivors are in the other buffer
+  const size_t k = std::min<size_t>(P.wcap, tot);
+  if (k) HIPCHK(hipMemcpy(out, P.a.out, k * sizeof(jg_done_row), hipMemcpyDeviceToHost));
+  if (k && !peek) t.cur ^= 1, t.n -= k;  // the survivors are in the other buffer
+  return JG_OK;
+}
+
+// the rules of jg_engine_await_blocks for rows that are about to be registered on a single-device engine
+int await_rows_check(const jg_engine* e, const jg_await_row* rows, size_t n, const char* who) {
+  auto refuse = [&](const char* what) { return fail(JG_EINVAL, std::string(who) + ": " + what); };
+  for (size_t i = 0; i < n; i++) {
+    const jg_await_row& r = rows[i];
+    if (r.group >= e->cfg.n_groups) return refuse("group out of range");
+    if (r.flags || r.reserved) return refuse("flags and reserved must be 0");
+    if (!r.block_id) return refuse("block id 0 is never applied");
+  }
+  return JG_OK;
+}
+
+// ---- completions behind a kept node step (jg_step_node_awaited) ----------------------------------------------------------
+// the set's pinned words: the scan job and the head the device reads, then where the header block lands
+enum { NODE_AWAIT_JOB = 0, NODE_AWAIT_HEAD = 2, NODE_AWAIT_HDR = 4, NODE_AWAIT_PINNED_WORDS = NODE_AWAIT_HDR + JG_AH_WORDS };
+static_assert(sizeof(JgScanJob) <= 16, "the job fits in front of the head");
+
+// the host's bound on the waiters outstanding: as of the newest viewed step or synchronous call, plus what the steps begun
+// since register
+size_t node_await_bound(const jg_engine* e) {
+  size_t b = e->await.n;
+  for (const jg_engine::NodeOut& o : e->node.sets)
+    if (o.out && o.aw.on) b += o.aw.m;
+  return b;
+}
+
+// the step's rows into the set's pinned memory (the set is the step's from here on; whatever read it last has been viewed)
+int node_await_stage(jg_engine::NodeOut& o, const jg_await_row* rows) {
+  const size_t bytes = o.aw.m * sizeof(jg_await_row);
+  o.l_await_up.n = 0;
+  if (!bytes) return JG_OK;
+  HIPCHK(o.l_await_up.reserve(bytes));
+  std::memcpy(o.l_await_up.p, rows, bytes);
+  return JG_OK;
+}
+
+// The completion request of kept step `o`, queued behind the kernels of that step (and its poll) that are in the stream by
+// now, and its trip home on the down stream: the header block as one copy, the done rows sized from the awaited step
+// finished last (the rest is fetched when the step is viewed: node_await_finish).  The first pass sends the staged rows up,
+// behind the step, and - if no awaited step is outstanding, so that the host's n and cur are the table's - writes the head
+// from them, in the stream.  `gate`: as for node_poll_tail.  Synchronises nothing.
+int node_await_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate) {
+  jg_engine::NodeStep& nd = e->node;
+  jg_engine::NodeAwait& aw = o.aw;
+  jg_engine::AwaitTable& t = e->await;
+  AwaitPlan P;
+  await_plan(P, true, aw.bound, aw.m, aw.cap);
+  if (!aw.scratch) HIPCHK(e->arenas[o.arena].alloc(P.c.at, (void**)&aw.scratch));  // (the pass behind the catch-up pass: the same block)
+  if (!o.h_await) {
+    HIPCHK(hipHostMalloc((void**)&o.h_await, NODE_AWAIT_PINNED_WORDS * 8, hipHostMallocDefault));
+    std::memset(o.h_await, 0, NODE_AWAIT_PINNED_WORDS * 8);
+  }
+  char* const B = aw.scratch;
+  await_bind(e, P, B, aw.peek, aw.stats, aw.now_ms, 0, gate);
+  if (!aw.redone) {
+    if (aw.m) HIPCHK(hipMemcpyAsync(B + P.o_rows, o.l_await_up.p, aw.m * sizeof(jg_await_row), hipMemcpyHostToDevice, e->stream));
+    const jg_engine::NodeOut& other = nd.sets[(&o - nd.sets) ^ 1];
+    if (!(other.out && other.aw.on)) {  // (the step before, if it is outstanding and awaited, leaves the head behind its chain)
+      JgAwaitHead* const h = (JgAwaitHead*)(o.h_await + NODE_AWAIT_HEAD);
+      *h = JgAwaitHead{(uint32_t)t.n, (uint32_t)t.cur, {0u, 0u}};
+      HIPCHK(hipMemcpyAsync(t.misc + AWT_O_HEAD, h, sizeof *h, hipMemcpyHostToDevice, e->stream));
+    }
+  }
+  *(JgScanJob*)(o.h_await + NODE_AWAIT_JOB) = JgScanJob{t.bsum, P.tiles, 0};
+  if (const int rc = await_queue(e, P, (const JgScanJob*)(o.h_await + NODE_AWAIT_JOB), aw.stats)) return rc;
+  HIPCHK(hipEventRecord(o.ev_kernels, e->stream));
+  HIPCHK(hipStreamWaitEvent(nd.down, o.ev_kernels, 0));
+  HIPCHK(hipMemcpyAsync(o.h_await + NODE_AWAIT_HDR, P.k.hdr, JG_AH_WORDS * 8, hipMemcpyDeviceToHost, nd.down));
+  if (!aw.redone) {  // (the pass behind the catch-up pass lands where the first one did: its copy may still be in flight)
+    const size_t last = nd.await_guess_known ? nd.await_guess : P.wcap;  // (no awaited step finished yet: min(cap, bound))
+    aw.copied = std::min(P.wcap, last + last / 32 + 4096);               // (the margin of the fsm rows: node_keep_tail)
+  }
+  if (const size_t bytes = aw.copied * sizeof(jg_done_row)) {
+    o.l_await.n = 0;
+    HIPCHK(o.l_await.reserve(bytes));
+    HIPCHK(hipMemcpyAsync(o.l_await.p, P.k.out, bytes, hipMemcpyDeviceToHost, nd.down));
+  }
+  return JG_OK;
+}
+
+// Kept step `o` is being viewed and its outputs have landed: the header block says what was delivered - the rows the step's
+// own copy did not bring are fetched now - and what the table's head is behind the step: the host's n, cur and bound follow
+// it.  The answer is what jg_node_await_view hands out from here on.  Before the set's arena starts over.
+int node_await_finish(jg_engine* e, jg_engine::NodeOut& o) {
+  jg_engine::NodeStep& nd = e->node;
+  jg_engine::NodeAwait& aw = o.aw;
+  jg_engine::AwaitTable& t = e->await;
+  jg_node_await& v = o.await_view;
+  v = jg_node_await{};
+  if (!aw.on) return JG_OK;
+  const uint64_t* const h = o.h_await + NODE_AWAIT_HDR;
+  if (h[JG_AH_GATE]) return fail(JG_EDEVICE, "internal: an awaited step's chain was gated and not queued again");
+  AwaitPlan P;
+  await_plan(P, true, aw.bound, aw.m, aw.cap);
+  const size_t given = (size_t)h[JG_AH_GIVEN];
+  if (given > P.wcap || h[JG_AH_N] > t.cap) return fail(JG_EDEVICE, "internal: an awaited step's header block is out of range");
+  if (given > aw.copied) {
+    o.l_await.n = aw.copied * sizeof(jg_done_row);  // (what has landed moves along if the buffer grows)
+    HIPCHK(o.l_await.reserve(given * sizeof(jg_done_row)));
+    HIPCHK(hipMemcpyAsync(o.l_await.p + aw.copied * sizeof(jg_done_row), aw.scratch + P.o_out + aw.copied * sizeof(jg_done_row),
+                          (given - aw.copied) * sizeof(jg_done_row), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  nd.await_guess = (size_t)h[JG_AH_TOTAL], nd.await_guess_known = true;
+  t.n = (size_t)h[JG_AH_N], t.cur = (int)(h[JG_AH_CUR] & 1u);
+  v.attached = 1u, v.state = aw.redone ? (uint32_t)JG_NODE_POLL_REDONE : 0u;
+  v.rows = given ? (const jg_done_row*)o.l_await.p : nullptr;
+  v.rows_n = given, v.total = (size_t)h[JG_AH_TOTAL];
+  if (aw.stats) {  // (jg_await_stats is the stat words in order, then left: jg_await.h)
+    std::memcpy(&v.stats, h + JG_AH_STATS, JG_AWT_WORDS * 8);
+    v.stats.left = h[JG_AH_LEFT];
+  }
+  aw.scratch = nullptr;  // (the arena's: gone with it)
   return JG_OK;
 }
 
@@ -120,12 +302,7 @@ int jg_engine_await_blocks(jg_engine* e, const jg_await_row* rows, size_t n) {
   if (!e || (n && !rows)) return fail(JG_EINVAL, "null argument");
   if (const int rc = refuse_first(e, kept_refuse)) return rc;
   if (!shard_at(e, 0)->await.cap) return fail(JG_EINVAL, "jg_engine_await_blocks: no open table (jg_engine_await_open)");
-  for (size_t i = 0; i < n; i++) {
-    const jg_await_row& r = rows[i];
-    if (r.group >= e->cfg.n_groups) return fail(JG_EINVAL, "jg_engine_await_blocks: group out of range");
-    if (r.flags || r.reserved) return fail(JG_EINVAL, "jg_engine_await_blocks: flags and reserved must be 0");
-    if (!r.block_id) return fail(JG_EINVAL, "jg_engine_await_blocks: block id 0 is never applied");
-  }
+  if (const int rc = await_rows_check(e, rows, n, "jg_engine_await_blocks")) return rc;
   if (!e->router) {
     if (e->await.n + n > e->await.cap) return fail(JG_ECAPACITY, "jg_engine_await_blocks: the table is full");
     HIPCHK(hipSetDevice(e->device));

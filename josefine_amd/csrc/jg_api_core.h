@@ -335,7 +335,9 @@ struct jg_engine {
   uint4* commit_shadow = nullptr;
   // jg_engine_await_open: the completion feed's table (jg_await.h) - two buffers of `cap` waiters, of which buf[cur] holds
   // the n outstanding ones in registration order, a verdict byte per waiter, the tile counts / prefixes, the partial stat
-  // records and one block for the total, the stats and the scan job
+  // records and one block for the total, the stats, the scan job and the table's HEAD on the device ({n, cur}: what the
+  // chain of an awaited node step reads and its header kernel writes).  n and cur are authoritative while no awaited step
+  // is outstanding; while one is, the device's head is, and they are refreshed from the header block at every view
   struct AwaitTable {
     uint4* buf[2] = {nullptr, nullptr};
     uint8_t* verdict = nullptr;
@@ -438,6 +440,18 @@ struct jg_engine {
     size_t copied[3] = {0, 0, 0};      // rows of each feed the step's own copy brought home
     bool redone = false;               // queued once more, ungated, behind the catch-up pass (JG_NODE_POLL_REDONE)
   };
+  // the completion request of a kept node step: jg_node_await_request's fields, and the step's own bookkeeping
+  struct NodeAwait {
+    bool on = false;                   // the step carries a request
+    size_t m = 0;                      // rows registered first (staged in NodeOut::l_await_up)
+    bool peek = false, stats = false;
+    uint64_t now_ms = 0;
+    size_t cap = 0;
+    size_t bound = 0;                  // the host's bound on the waiters behind the registration: what the chain is launched for
+    char* scratch = nullptr;           // the set's arena: the staged rows, the done rows, the header block
+    size_t copied = 0;                 // done rows the step's own copy brought home
+    bool redone = false;               // queued once more, ungated, behind the catch-up pass (JG_NODE_POLL_REDONE)
+  };
   struct NodeOut {
     jg_leader_beat* h_beat = nullptr;  // pinned mirrors of the outbox columns
     uint64_t *h_ae = nullptr, *h_answer = nullptr, *h_hbc = nullptr, *h_aec = nullptr;
@@ -475,6 +489,12 @@ struct jg_engine {
     uint64_t* h_poll = nullptr;        // pinned: the scan jobs the device reads, then where the header block lands
     PinnedQueue<char> l_poll[3];       // pinned: where each feed's rows land (bytes); the first poll.copied[x] rows came with the step
     jg_node_poll poll_view{};          // what jg_node_poll_view hands out once the step's outbox has been viewed
+    // -- jg_step_node_awaited: the completion request that travels with the step (jg_api_await.h) --------------------------
+    NodeAwait aw;                      // the request as copied at entry (on == false: the step carries none)
+    uint64_t* h_await = nullptr;       // pinned: the scan job and the head the device reads, then where the header block lands
+    PinnedQueue<char> l_await_up;      // pinned: the step's staged rows on their way up (bytes)
+    PinnedQueue<char> l_await;         // pinned: where the done rows land (bytes); the first aw.copied rows came with the step
+    jg_node_await await_view{};        // what jg_node_await_view hands out once the step's outbox has been viewed
   };
   struct NodeStep {
     // The two sets.  `newest` is the one the newest step took (a kept step takes the other one, a plain step the same one
@@ -487,6 +507,8 @@ struct jg_engine {
     int poll_viewed = -1;              // the set whose kept step's outbox view finished last (jg_node_poll_view answers for it)
     size_t poll_guess[3] = {0, 0, 0};  // the feed totals of the polled step finished last: what sizes the next step's row copies
     bool poll_guess_known = false;
+    size_t await_guess = 0;            // the done waiters of the awaited step finished last: what sizes the next step's row copy
+    bool await_guess_known = false;
     bool ready = false;
     JgNodeCols cols{};
     uint64_t *h_in_answers = nullptr, *h_in_hbc = nullptr;  // pinned [R][G]: column inbound (jg_node_inbox_columns)

@@ -216,12 +216,14 @@ void jg_engine_destroy(jg_engine* e) {
     (void)hipStreamDestroy(e->node.down);
   }
   for (jg_engine::NodeOut& o : e->node.sets) {  // (node_set_ensure, node_keep_ensure)
-    for (void* p : {(void*)o.h_beat, (void*)o.h_ae, (void*)o.h_answer, (void*)o.h_hbc, (void*)o.h_nsparse, (void*)o.h_aec, (void*)o.h_status, (void*)o.h_poll})
+    for (void* p : {(void*)o.h_beat, (void*)o.h_ae, (void*)o.h_answer, (void*)o.h_hbc, (void*)o.h_nsparse, (void*)o.h_aec, (void*)o.h_status, (void*)o.h_poll,
+                    (void*)o.h_await})
       if (p) (void)hipHostFree(p);
     for (hipEvent_t ev : {o.ev_out, o.ev_early, o.ev_kernels})
       if (ev) (void)hipEventDestroy(ev);
     o.l_fsm.destroy();
     for (PinnedQueue<char>& q : o.l_poll) q.destroy();
+    o.l_await_up.destroy(), o.l_await.destroy();
   }
   if (e->node.ev_cols) (void)hipEventDestroy(e->node.ev_cols);
   e->q_msgs.destroy();

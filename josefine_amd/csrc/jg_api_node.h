@@ -107,6 +107,11 @@ int node_fsm_record(jg_engine* e, StepRec& rec, uint32_t flags);
 // (jg_api_poll.h) the poll that travels with a kept step: queued behind its kernels, collected when its outbox is viewed
 int node_poll_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate);
 int node_poll_finish(jg_engine* e, jg_engine::NodeOut& o);
+// (jg_api_await.h) the completion request that travels with a kept step: staged at entry, queued behind its kernels (and its
+// poll), collected when its outbox is viewed
+int node_await_stage(jg_engine::NodeOut& o, const jg_await_row* rows);
+int node_await_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate);
+int node_await_finish(jg_engine* e, jg_engine::NodeOut& o);
 
 // node_step (or node_settle's catch-up pass) is running: its halves' own node_settle calls are not another caller's
 struct InStep {
@@ -415,8 +420,10 @@ int node_publish(jg_engine* e, const NodeRun& s, uint32_t seq0, NodeClaim& claim
   return JG_OK;
 }
 
-// `poll`: the request of a polled step (jg_step_node_polled: checked, and a kept step's), or null
-int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::NodePoll* poll) {
+// `poll`: the request of a polled step (jg_step_node_polled: checked, and a kept step's), or null; `await`: the completion
+// request of an awaited step (jg_step_node_awaited: checked, its bound taken) and the rows it registers, or null
+int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::NodePoll* poll, const jg_engine::NodeAwait* await,
+              const jg_await_row* await_rows) {
   static const bool trace = std::getenv("JG_TRACE_NODE") != nullptr;
   jg_engine::NodeStep& nd = e->node;
   NodeRun s;
@@ -433,6 +440,8 @@ int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::No
   o.keep = s.keep, o.pending.on = false;
   if (nd.poll_viewed == (int)nd.newest) nd.poll_viewed = -1;  // (the answer viewed last lived in this set)
   o.poll = poll ? *poll : jg_engine::NodePoll{};
+  o.aw = await ? *await : jg_engine::NodeAwait{};
+  if (o.aw.on && (rc = node_await_stage(o, await_rows))) return rc;  // (the rows are the caller's until here)
   if (s.keep) {  // (the set starts empty: its last step's regions went with that step's arena)
     o.set = e->cur_set, o.arena = e->cur_arena, o.irr_gen = e->irr_gen;
     o.d_fsm_cnt = nullptr, o.d_fsm = o.d_stage = nullptr, o.d_bsum = nullptr;
@@ -453,6 +462,7 @@ int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::No
   if ((rc = node_tail(e, s))) return rc;
   // the poll behind the step: gated by the step's own general-row count, final once the route pass has run (no rows: no gate)
   if (o.poll.want && (rc = node_poll_tail(e, o, s.n ? nd.d_nsparse : nullptr))) return rc;
+  if (o.aw.on && (rc = node_await_tail(e, o, s.n ? nd.d_nsparse : nullptr))) return rc;
   if ((rc = node_publish(e, s, seq0, claim))) return rc;
   if (trace)
     std::fprintf(stderr, "[jg node] %zu rows: uploads + classify + route issued in %.0f us, waited %.0f us (H2D %.1f MB), halves + fsm build + outbox copies issued in %.0f us\n",
@@ -621,6 +631,10 @@ int node_settle(jg_engine* e) {
       o.poll.redone = true;
       if ((rc = node_poll_tail(e, o, nullptr))) return rc;
     }
+    if (o.aw.on) {  // ... and its completion request: the gated chain appended nothing, removed nothing and left the head alone
+      o.aw.redone = true;
+      if ((rc = node_await_tail(e, o, nullptr))) return rc;
+    }
     HIPCHK(hipEventRecord(o.ev_out, nd.down));
   }
   for (StepRec& rec : e->recs)
@@ -722,6 +736,7 @@ int node_keep_finish(jg_engine* e, jg_engine::NodeOut& o) {
   if (e->track_segs) seg_add(e->seg_f, o.seq_hi, total);
   nd.fsm_guess = total, nd.fsm_guess_known = true;
   if ((rc = node_poll_finish(e, o))) return rc;  // (the rows its own copy did not bring: out of the arena, before it starts over)
+  if ((rc = node_await_finish(e, o))) return rc;
   // everything the step allocated has been read - d_stage just above was the last: its arena starts over, here and nowhere
   // else (records, if it had any, were drained above)
   e->arenas[o.arena].reset();

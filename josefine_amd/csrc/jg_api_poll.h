@@ -9,8 +9,9 @@
 // handle is served shard by shard: sized, then delivered.  And jg_step_node_polled /
 // jg_node_poll_view (ABI v21): the same chain queued BEHIND a kept node step over scratch of the step's own arena, gated on
 // the device by the step's general-row count, its header and rows sent home on the step's trip and handed out when the
-// step's outbox is viewed (node_poll_tail, node_poll_finish: called by jg_api_node.h).  Part of josefine_gpu.hip's one
-// translation unit.
+// step's outbox is viewed (node_poll_tail, node_poll_finish: called by jg_api_node.h).  And jg_step_node_awaited /
+// jg_node_await_view (ABI v23): the one entry point of a kept step with attachments - the poll, the completion request of
+// jg_api_await.h, or both.  Part of josefine_gpu.hip's one translation unit.
 #pragma once
 
 namespace {
@@ -472,27 +473,57 @@ int jg_engine_poll(jg_engine* e, jg_poll* p) {
 }
 
 int jg_step_node_polled(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_poll* request) {
-  if (!request) return jg_step_node(e, now_ms, flags);
+  return jg_step_node_awaited(e, now_ms, flags, request, nullptr);
+}
+
+int jg_step_node_awaited(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_poll* request, const jg_node_await_request* await) {
+  if (!request && !await) return jg_step_node(e, now_ms, flags);
+  const char* const who = await ? "jg_step_node_awaited" : "jg_step_node_polled";
   if (!e) return fail(JG_EINVAL, "null argument");
   if (!(flags & (JG_NODE_LEADER_HALF | JG_NODE_FOLLOWER_HALF)) || (flags & ~127u))
-    return fail(JG_EINVAL, "jg_step_node_polled: flags = JG_NODE_LEADER_HALF and / or JG_NODE_FOLLOWER_HALF [| JG_NODE_TICK] | JG_NODE_ASYNC [| JG_NODE_COMMON_AE] [| JG_NODE_FSM_FUSED] | JG_NODE_KEEP");
-  if (e->router) return fail(JG_EINVAL, "jg_step_node_polled: a polled step is a shard's (jg_get_shard): JG_NODE_KEEP is per shard");
+    return fail(JG_EINVAL, std::string(who) + ": flags = JG_NODE_LEADER_HALF and / or JG_NODE_FOLLOWER_HALF [| JG_NODE_TICK] | JG_NODE_ASYNC [| JG_NODE_COMMON_AE] [| JG_NODE_FSM_FUSED] | JG_NODE_KEEP");
+  if (e->router) return fail(JG_EINVAL, std::string(who) + ": a polled or awaited step is a shard's (jg_get_shard): JG_NODE_KEEP is per shard");
   if (!(flags & JG_NODE_KEEP) || !(flags & JG_NODE_ASYNC))
-    return fail(JG_EINVAL, "jg_step_node_polled: a poll travels with a kept step: JG_NODE_ASYNC | JG_NODE_KEEP");
-  if (const int rc = poll_check(e, request, false)) return rc;
+    return fail(JG_EINVAL, std::string(who) + ": a poll and a completion request travel with a kept step: JG_NODE_ASYNC | JG_NODE_KEEP");
+  if (request)
+    if (const int rc = poll_check(e, request, false)) return rc;
+  jg_engine::NodeAwait aw;  // (*await: copied here; its rows once the step has its set - node_await_stage)
+  if (await) {
+    if (await->n && !await->rows) return fail(JG_EINVAL, "null argument");
+    if (!e->await.cap) return fail(JG_EINVAL, "jg_step_node_awaited: no open table (jg_engine_await_open)");
+    if (const int rc = await_rows_check(e, await->rows, await->n, who)) return rc;
+    if (await->flags & ~(uint32_t)JG_WATCH_PEEK) return fail(JG_EINVAL, "jg_step_node_awaited: unknown flag");
+    if (await->want_stats > 1u) return fail(JG_EINVAL, "jg_step_node_awaited: want_stats is 0 or 1");
+    if (await->now_ms == UINT64_MAX) return fail(JG_EINVAL, "jg_step_node_awaited: now_ms out of range");
+    const size_t bound = node_await_bound(e);
+    if (await->n > e->await.cap || bound + await->n > e->await.cap)
+      return fail(JG_ECAPACITY, "jg_step_node_awaited: the table is full (by the bound: the outstanding steps' watches have not been viewed)");
+    aw.on = true, aw.m = await->n, aw.peek = (await->flags & JG_WATCH_PEEK) != 0, aw.stats = await->want_stats != 0;
+    aw.now_ms = await->now_ms, aw.cap = await->cap, aw.bound = bound + await->n;
+  }
   if (e->inflight.phase) return fail(JG_EINVAL, "a drain is in transfer: jg_drain_wait first");
   jg_engine::NodePoll np;  // (*request and *request->clock: copied here)
-  np.want = request->want, np.g0 = request->g0, np.n = request->n;
-  const bool on[3] = {(np.want & JG_POLL_LEADERS) != 0, (np.want & JG_POLL_REPLICAS) != 0, (np.want & JG_POLL_COMMITS) != 0};
-  const uint32_t fl[3] = {request->leader_flags, request->replica_flags, request->commit_flags};
-  const size_t cap[3] = {request->leaders_cap, request->replicas_cap, request->commits_cap};
-  for (int x = 0; x < 3; x++) np.peek[x] = on[x] && (fl[x] & JG_WATCH_PEEK), np.cap[x] = on[x] ? cap[x] : 0;
-  np.commits_only = on[POLL_C] && (request->commit_flags & JG_WATCH_COMMITS_ONLY);
-  np.backlog = on[POLL_C] && request->backlog;
-  np.timed = on[POLL_I] && request->clock;
-  if (np.timed) np.clk = *request->clock;
-  np.pol = request->policy, np.lag_limit = request->census_lag_limit;
-  return node_step(e, now_ms, flags, &np);
+  if (request) {
+    np.want = request->want, np.g0 = request->g0, np.n = request->n;
+    const bool on[3] = {(np.want & JG_POLL_LEADERS) != 0, (np.want & JG_POLL_REPLICAS) != 0, (np.want & JG_POLL_COMMITS) != 0};
+    const uint32_t fl[3] = {request->leader_flags, request->replica_flags, request->commit_flags};
+    const size_t cap[3] = {request->leaders_cap, request->replicas_cap, request->commits_cap};
+    for (int x = 0; x < 3; x++) np.peek[x] = on[x] && (fl[x] & JG_WATCH_PEEK), np.cap[x] = on[x] ? cap[x] : 0;
+    np.commits_only = on[POLL_C] && (request->commit_flags & JG_WATCH_COMMITS_ONLY);
+    np.backlog = on[POLL_C] && request->backlog;
+    np.timed = on[POLL_I] && request->clock;
+    if (np.timed) np.clk = *request->clock;
+    np.pol = request->policy, np.lag_limit = request->census_lag_limit;
+  }
+  return node_step(e, now_ms, flags, request ? &np : nullptr, await ? &aw : nullptr, await ? await->rows : nullptr);
+}
+
+int jg_node_await_view(jg_engine* e, jg_node_await* out) {
+  if (!e || !out) return fail(JG_EINVAL, "null argument");
+  if (e->router) return fail(JG_EINVAL, "jg_node_await_view: an awaited step is a shard's (jg_get_shard)");
+  if (e->node.poll_viewed < 0) return fail(JG_EINVAL, "jg_node_await_view: no kept step's outbox has been viewed (or a newer step has claimed its set)");
+  *out = e->node.sets[e->node.poll_viewed].await_view;
+  return JG_OK;
 }
 
 int jg_node_poll_view(jg_engine* e, jg_node_poll* out) {

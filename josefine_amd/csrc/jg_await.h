@@ -146,3 +146,164 @@ __global__ __launch_bounds__(JG_BLOCK) void k_await_write(JgDev d, JgAwaitArgs a
   out[1] = jg_u32x4{w1.x, w1.y, lo(term_now), hi(term_now)};
   out[2] = jg_u32x4{lo(commit), hi(commit), lo(head), hi(head)};
 }
+
+// ---- the feed behind a kept node step (jg_step_node_awaited) --------------------------------------------------------------
+// With kept steps outstanding the host knows neither how many waiters the table holds nor which buffer holds them: both are
+// the outcome of watches whose totals have not come home.  So the table has a HEAD on the device, {n, cur}, and the chain
+// of an awaited step reads it there:
+//
+//   k_await_append      the step's m staged rows (its arena's, uploaded behind the step) to buf[cur] + n * 3: one 16-byte
+//                       piece a lane, consecutive lanes consecutive pieces; the head read once per workgroup, never written
+//   k_await_count_kept  k_await_count over n_eff = head.n + m waiters of buf[head.cur], launched for the host's BOUND on
+//   k_await_write_kept  n_eff (`tiles`); a tile wholly beyond n_eff counts 0 / returns, so the one scan over `tiles` holds
+//   k_await_header      one workgroup behind them: the partial stat records folded (k_await_stats_sum's job), the answer but
+//                       the rows as ONE block - and then, alone of the chain, the head: n = n_eff - removed, cur flipped if
+//                       something was removed.  Every kernel before it read the same head
+//
+// `gate` is the step's general-row count on the device (null: no gate), one scalar load per workgroup: nonzero, and the
+// whole chain leaves table, head and rows alone - the header block says so - for the same request is queued once more,
+// ungated, behind the step's catch-up pass.  An append that ran in both would register every waiter twice.
+struct JgAwaitHead {
+  uint32_t n, cur, pad[2];
+};
+static_assert(sizeof(JgAwaitHead) == 16, "the table's head is one 16-byte record");
+
+// the header block of an awaited step, 8-byte words
+#define JG_AH_TOTAL 0u    // the done waiters
+#define JG_AH_GIVEN 1u    // min(cap, total): the rows delivered
+#define JG_AH_STATS 2u    // [JG_AWT_WORDS] the stats before the delivery (zero unless wanted)
+#define JG_AH_LEFT (JG_AH_STATS + JG_AWT_WORDS)  // the waiters outstanding behind the call
+#define JG_AH_N (JG_AH_LEFT + 1u)                // the head as this pass leaves it
+#define JG_AH_CUR (JG_AH_N + 1u)
+#define JG_AH_GATE (JG_AH_CUR + 1u)              // the gate's verdict: the step's general-path rows as this pass saw them
+#define JG_AH_WORDS (JG_AH_GATE + 1u)
+
+struct JgAwaitKeptArgs {
+  uint32_t m;       // staged rows, appended first
+  uint32_t room;    // the table's capacity in waiters
+  uint32_t peek;    // 1: rows only, nothing is removed
+  uint32_t tiles;   // tiles of JG_AWT_TILE waiters of the host's bound on n_eff
+  uint32_t parts;   // workgroups of the count pass (<= JG_AWT_PARTS)
+  uint32_t stats;   // 1: the stats are wanted
+  uint64_t now;     // now_ms
+  uint64_t cap;     // rows the caller takes
+  JgAwaitHead* head;
+  const uint32_t* gate;  // or null
+  const uint4* rows;     // [m][3] the staged rows
+  uint4* buf[2];         // the table's two buffers
+  uint8_t* verdict;
+  uint64_t* bsum;         // [tiles]
+  uint64_t* part;         // [parts][JG_AWT_WORDS]
+  const uint64_t* total;  // [1] (k_scan_block_sums)
+  uint4* out;             // [cap] rows of three 16-byte pieces (device)
+  uint64_t* hdr;          // [JG_AH_WORDS]
+};
+
+__device__ __forceinline__ bool jg_await_gated(const uint32_t* gate) { return gate && *gate; }
+// the waiters of the table once the step's rows are behind them; never beyond the room (the host's bound keeps it so)
+__device__ __forceinline__ uint32_t jg_await_n_eff(const JgAwaitKeptArgs& a, uint32_t n) {
+  const uint64_t e = (uint64_t)n + a.m;
+  return e > a.room ? a.room : (uint32_t)e;
+}
+
+__global__ __launch_bounds__(JG_BLOCK) void k_await_append(JgAwaitKeptArgs a) {
+  if (jg_await_gated(a.gate)) return;
+  const uint32_t n = a.head->n, cur = a.head->cur & 1u;  // (uniform: once per workgroup)
+  if ((uint64_t)n + a.m > a.room) return;                // (never taken: refused by the host's bound)
+  const size_t i = (size_t)blockIdx.x * JG_BLOCK + threadIdx.x;
+  if (i < (size_t)a.m * 3) a.buf[cur][(size_t)n * 3 + i] = a.rows[i];
+}
+
+__global__ __launch_bounds__(JG_BLOCK) void k_await_count_kept(JgDev d, JgAwaitKeptArgs a) {
+  if (jg_await_gated(a.gate)) return;
+  const uint32_t n = jg_await_n_eff(a, a.head->n);
+  const uint4* tab = a.buf[a.head->cur & 1u];
+  uint32_t bc[JG_AWT_WORDS] = {0u, 0u, 0u, 0u, 0u};  // wave-uniform (every lane adds the same popcount)
+  for (uint32_t tile = blockIdx.x; tile < a.tiles; tile += a.parts) {  // (uniform over the workgroup)
+    if ((uint64_t)tile * JG_AWT_TILE >= n) {  // (uniform) wholly beyond the table: the bound was not reached
+      if (threadIdx.x == 0) a.bsum[tile] = 0;
+      continue;
+    }
+    const uint32_t i = tile * JG_AWT_TILE + threadIdx.x;
+    const bool in = i < n;
+    const size_t at = (size_t)(in ? i : 0u) * 3;
+    const uint4 w0 = tab[at], w1 = tab[at + 1], w2 = tab[at + 2];
+    const uint32_t g = w0.x < d.G ? w0.x : 0u;  // (checked at registration: never taken)
+    const uint32_t f = d.flags[g];
+    const uint64_t term_now = d.term[g], head = d.head[g], pw = d.mlag[g], col = d.commit[g], run_hi = d.run_hi[g];
+    const uint64_t commit = jg_read_commit(d, g, f);
+    asm volatile("" ::"v"(f), "v"(term_now), "v"(head), "v"(pw), "v"(col), "v"(run_hi));  // (as in k_await_count: one round trip)
+    const uint32_t role = f & JGF_ROLE_MASK, fault = (f & JGF_FAULT_MASK) >> JGF_FAULT_SHIFT;
+    const uint32_t v = in ? jg_await_verdict(role, fault, term_now, commit, jg_awt_u64(w1.x, w1.y), jg_awt_u64(w1.z, w1.w),
+                                             jg_awt_u64(w2.x, w2.y), a.now)
+                          : 0u;
+    if (in) a.verdict[i] = (uint8_t)v;
+    const uint64_t m = __ballot(in && v);
+    bc[0] += __popcll(__ballot(in && !v));
+    bc[1] += __popcll(m);
+    bc[2] += __popcll(__ballot(in && (v & JG_DONE_APPLIED)));
+    bc[3] += __popcll(__ballot(in && (v & JG_DONE_LOST)));
+    bc[4] += __popcll(__ballot(in && (v & JG_DONE_EXPIRED)));
+    const uint32_t t = jg_tile_count(__popcll(m));
+    if (threadIdx.x == 0) a.bsum[tile] = t;
+    __syncthreads();  // (jg_tile_count's LDS is the next tile's too)
+  }
+  const uint64_t vals[JG_AWT_WORDS] = {bc[0], bc[1], bc[2], bc[3], bc[4]};
+  jg_block_words<JG_AWT_WORDS>(vals, JgNeverMax(), a.part);
+}
+
+__global__ __launch_bounds__(JG_BLOCK) void k_await_write_kept(JgDev d, JgAwaitKeptArgs a) {
+  if (jg_await_gated(a.gate)) return;
+  const uint64_t total = *a.total;
+  if ((total < a.cap ? total : a.cap) == 0) return;  // (uniform over the launch) nothing is delivered: the table stays as it is
+  const uint32_t n = jg_await_n_eff(a, a.head->n), cur = a.head->cur & 1u;
+  if ((uint64_t)blockIdx.x * JG_AWT_TILE >= n) return;  // (uniform over the workgroup) wholly beyond the table
+  const uint64_t base = a.bsum[blockIdx.x];
+  if (a.peek && base >= a.cap) return;  // (uniform over the workgroup) a peek copies no waiter: wholly beyond cap
+  const uint4* tab = a.buf[cur];
+  uint4* dst = a.buf[cur ^ 1u];
+  const uint32_t i = blockIdx.x * JG_AWT_TILE + threadIdx.x;
+  const bool in = i < n;
+  const uint32_t v = in ? a.verdict[i] : 0u;
+  const uint64_t rank = base + jg_rank_in_tile(__ballot(in && v));  // the done waiters before this one
+  if (!in) return;
+  const bool deliver = v && rank < a.cap;
+  if (!deliver && a.peek) return;
+  const size_t at = (size_t)i * 3;
+  const uint4 w0 = tab[at], w1 = tab[at + 1], w2 = tab[at + 2];
+  if (!deliver) {  // a survivor: behind it min(rank, cap) waiters leave
+    const size_t to = ((size_t)i - (size_t)(rank < a.cap ? rank : a.cap)) * 3;
+    dst[to] = w0, dst[to + 1] = w1, dst[to + 2] = w2;
+    return;
+  }
+  const uint32_t g = w0.x < d.G ? w0.x : 0u;
+  const uint32_t f = d.flags[g];
+  const uint64_t term_now = d.term[g], head = d.head[g];
+  const uint64_t commit = jg_read_commit(d, g, f);
+  const uint32_t role = f & JGF_ROLE_MASK, fault = (f & JGF_FAULT_MASK) >> JGF_FAULT_SHIFT, self = (f & JGF_SELF_MASK) >> JGF_SELF_SHIFT;
+  auto lo = [](uint64_t x) { return (uint32_t)x; };
+  auto hi = [](uint64_t x) { return (uint32_t)(x >> 32); };
+  jg_u32x4* out = (jg_u32x4*)a.out + rank * 3;  // (the row of k_await_write)
+  out[0] = jg_u32x4{g, v | role << 8 | fault << 16 | self << 24, w0.z, w0.w};
+  out[1] = jg_u32x4{w1.x, w1.y, lo(term_now), hi(term_now)};
+  out[2] = jg_u32x4{lo(commit), hi(commit), lo(head), hi(head)};
+}
+
+__global__ __launch_bounds__(JG_BLOCK) void k_await_header(JgAwaitKeptArgs a) {
+  const uint32_t gate = a.gate ? *a.gate : 0u;
+  if (gate) {  // (uniform) the pass left everything alone
+    if (threadIdx.x < JG_AH_WORDS) a.hdr[threadIdx.x] = threadIdx.x == JG_AH_GATE ? gate : 0ull;
+    return;
+  }
+  if (a.stats) jg_parts_reduce<JG_AWT_WORDS>(a.part, a.parts, a.hdr + JG_AH_STATS, JgNeverMax());
+  else if (threadIdx.x < JG_AWT_WORDS) a.hdr[JG_AH_STATS + threadIdx.x] = 0;
+  if (threadIdx.x) return;
+  const uint32_t n = jg_await_n_eff(a, a.head->n), cur = a.head->cur & 1u;
+  const uint64_t total = *a.total, given = total < a.cap ? total : a.cap;
+  const uint32_t removed = a.peek ? 0u : (uint32_t)given;
+  a.hdr[JG_AH_TOTAL] = total, a.hdr[JG_AH_GIVEN] = given;
+  a.hdr[JG_AH_LEFT] = a.hdr[JG_AH_N] = n - removed;
+  a.hdr[JG_AH_CUR] = removed ? cur ^ 1u : cur;
+  a.hdr[JG_AH_GATE] = 0;
+  a.head->n = n - removed, a.head->cur = removed ? cur ^ 1u : cur;
+}

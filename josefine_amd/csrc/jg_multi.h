@@ -256,7 +256,8 @@ int router_step(jg_engine* p, uint64_t now_ms) {
   return rc;
 }
 
-int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::NodePoll* poll);
+int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::NodePoll* poll, const jg_engine::NodeAwait* await = nullptr,
+              const jg_await_row* await_rows = nullptr);
 
 // jg_step_node on every shard (each one's rows were bucketed by jg_submit)
 int router_step_node(jg_engine* p, uint64_t now_ms, uint32_t flags) {

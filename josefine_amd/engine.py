@@ -428,18 +428,32 @@ class BatchedRaft(_Hosting):
         return self.node_outbox()
 
     def step_node_begin(self, now_ms: int = 0, leader: bool = True, follower: bool = True, tick: bool = True, async_: bool = False,
-                        common_ae: bool = False, fsm_fused: bool = False, keep: bool = False, poll: Optional[dict] = None) -> None:
+                        common_ae: bool = False, fsm_fused: bool = False, keep: bool = False, poll: Optional[dict] = None,
+                        completions: Optional[dict] = None) -> None:
         """jg_step_node alone (the outbox: `node_outbox`).  keep (JG_NODE_KEEP, with async_): the step keeps its outputs
         until its outbox is viewed - a second such step may be begun before that; `node_outbox` then serves the OLDER
         one and makes its rows the ones the next drains deliver.  poll (jg_step_node_polled, ABI v21; with keep): the
         keyword arguments of `poll` as a dict - the poll travels with the step, sees the engine exactly as the step leaves
-        it and is handed out by `node_poll` once the step's outbox has been viewed."""
+        it and is handed out by `node_poll` once the step's outbox has been viewed.  completions (jg_step_node_awaited,
+        ABI v23; with keep): dict(groups=, block_ids=, tokens=, terms=0, deadlines_ms=0, now_ms=, limit=None, peek=False,
+        stats=False) - the waiters of `await_blocks` (optional: without them the step only watches) are registered and the
+        watch of `watch_completions` is made behind the step; `node_completions` hands out the answer."""
         self._flush_pending()
         flags = (capi.NODE_LEADER_HALF if leader else 0) | (capi.NODE_FOLLOWER_HALF if follower else 0) | \
                 (capi.NODE_TICK if tick else 0) | (capi.NODE_ASYNC if async_ else 0) | \
                 (capi.NODE_COMMON_AE if common_ae else 0) | (capi.NODE_FSM_FUSED if fsm_fused else 0) | \
                 (capi.NODE_KEEP if keep else 0)
-        if poll is not None:
+        if completions is not None:
+            if not hasattr(self.api, "step_node_awaited"):
+                raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}step_node_awaited")
+            p = held = None
+            if poll is not None:
+                p, held, parts = self._poll_request(**poll)
+            req, rows, want_stats = self._await_request(**completions)  # (`rows`: what req points at, alive over the call)
+            self._check(self.api.step_node_awaited(self._h, int(now_ms), flags, C.byref(p) if p is not None else None, C.byref(req)))
+            del held
+            self._await_n = getattr(self, "_await_n", 0) + len(rows)  # (the bound: what the views take off it is not known yet)
+        elif poll is not None:
             if not hasattr(self.api, "step_node_polled"):
                 raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}step_node_polled")
             p, held, parts = self._poll_request(**poll)  # (`held`: what p points at, alive over the call)
@@ -449,6 +463,61 @@ class BatchedRaft(_Hosting):
             self._check(self.api.step_node(self._h, int(now_ms), flags))
         if keep:  # (what node_poll needs to know of the step and the view does not say: was the backlog asked for)
             self.__dict__.setdefault("_kept_backlog", []).append(bool(poll is not None and parts["backlog"]))
+            # (... and what node_completions needs: were the stats asked for, does the watch remove what it delivers)
+            self.__dict__.setdefault("_kept_await", []).append(
+                None if completions is None else (want_stats, not completions.get("peek", False)))
+
+    def _await_request(self, groups=(), block_ids=(), tokens=(), terms=0, deadlines_ms=0, now_ms: int = 0, limit: Optional[int] = None,
+                       peek: bool = False, stats: bool = False):
+        """jg_node_await_request from the keyword arguments of `await_blocks` and `watch_completions`"""
+        groups = np.atleast_1d(np.asarray(groups))
+        rows = np.zeros(len(groups), capi.AWAIT_ROW_DTYPE)
+        if len(groups) and (groups.min() < 0 or groups.max() > 0xFFFFFFFF):
+            raise EngineError(capi.EINVAL, "completions: group out of range")
+        rows["group"] = groups
+        for name, v in (("block_id", block_ids), ("token", tokens), ("term", terms), ("deadline_ms", deadlines_ms)):
+            rows[name] = np.asarray(v, dtype=np.uint64)
+        have = getattr(self, "_await_n", 0) + len(rows)
+        req = capi.NodeAwaitRequest()
+        req.rows, req.n = rows.ctypes.data if len(rows) else None, len(rows)
+        req.flags, req.want_stats, req.now_ms = capi.WATCH_PEEK if peek else 0, 1 if stats else 0, int(now_ms)
+        req.cap = have if limit is None else max(0, min(int(limit), have))
+        return req, rows, bool(stats)
+
+    def node_completions(self):
+        """jg_node_await_view: the answer of the completion request that travelled with the kept step whose outbox
+        `node_outbox` viewed last, as host copies: {"answer": what `watch_completions` returns for the same arguments -
+        (rows, total) or (rows, total, stats) - and "redone": the step had general-path rows and the chain ran behind its
+        catch-up pass (informational)}.  A step that carried no request: {"redone": False}."""
+        if not hasattr(self.api, "node_await_view"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}node_await_view")
+        v = capi.NodeAwait()
+        self._check(self.api.node_await_view(self._h, C.byref(v)))
+        if not v.attached:
+            return {"redone": False}
+        k = int(v.rows_n)
+        rows = np.zeros(0, capi.DONE_ROW_DTYPE)
+        if k:
+            buf = (C.c_char * (k * np.dtype(capi.DONE_ROW_DTYPE).itemsize)).from_address(v.rows)
+            rows = np.frombuffer(buf, dtype=capi.DONE_ROW_DTYPE).copy()
+        out = (rows, int(v.total))
+        if self.__dict__.get("_viewed_await_stats", False):
+            out += ({name: int(getattr(v.stats, name)) for name, _ in capi.AwaitStats._fields_},)
+        return {"answer": out, "redone": bool(v.state & capi.NODE_POLL_REDONE)}
+
+    def _view_await(self):
+        """behind a view of a kept step's outbox: the waiters its completion request removed leave the count that
+        `watch_completions` sizes its rows from"""
+        self._viewed_await_stats = False
+        kept = self.__dict__.get("_kept_await")
+        what = kept.pop(0) if kept else None
+        if what is None:
+            return
+        self._viewed_await_stats, removes = what
+        v = capi.NodeAwait()
+        self._check(self.api.node_await_view(self._h, C.byref(v)))
+        if removes:
+            self._await_n = getattr(self, "_await_n", 0) - int(v.rows_n)
 
     def node_poll(self) -> dict:
         """jg_node_poll_view: the answer of the poll that travelled with the kept step whose outbox `node_outbox` viewed
@@ -489,6 +558,7 @@ class BatchedRaft(_Hosting):
         self._check(self.api.node_outbox_view(self._h, C.byref(o)))
         if self.__dict__.get("_kept_backlog"):  # (kept steps were outstanding: the view served the oldest)
             self._viewed_backlog = self._kept_backlog.pop(0)
+            self._view_await()
         G, R = self.G, self.R
 
         def arr(p, dt, shape):

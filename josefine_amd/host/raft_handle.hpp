@@ -464,6 +464,13 @@ class BatchedRaft {
   // step_node_finish has served that step.  The answer is what poll(q) would have returned between that step and the next.
   void step_node_polled(uint64_t now_ms, uint32_t flags, const PollRequest& q) {
     flush_rows();
+    const jg_poll p = polled_words(q);
+    check(jg_step_node_polled(e_, now_ms, flags | (uint32_t)JG_NODE_ASYNC | (uint32_t)JG_NODE_KEEP, &p));
+    step_blocks_.emplace_back();
+    step_blocks_.back().swap(pending_blocks_);  // (as step_node_begin)
+  }
+  // the jg_poll of a polled step: the input fields only (q must outlive the call: its clock is pointed at)
+  jg_poll polled_words(const PollRequest& q) const {
     static jg_commit_backlog wanted;  // (never written through: the pointer only says that the backlog is wanted)
     jg_poll p{};
     p.want = q.want, p.g0 = q.g0, p.n = q.n == UINT32_MAX ? (uint32_t)stores_.size() - q.g0 : q.n;
@@ -475,9 +482,7 @@ class BatchedRaft {
     p.leaders_cap = std::min<size_t>(q.leaders_limit, p.n), p.replicas_cap = std::min<size_t>(q.replicas_limit, p.n);
     p.commits_cap = std::min<size_t>(q.commits_limit, p.n);
     p.backlog = &wanted;
-    check(jg_step_node_polled(e_, now_ms, flags | (uint32_t)JG_NODE_ASYNC | (uint32_t)JG_NODE_KEEP, &p));
-    step_blocks_.emplace_back();
-    step_blocks_.back().swap(pending_blocks_);  // (as step_node_begin)
+    return p;
   }
   // the poll of the kept step step_node_finish served last; *polled: that step carried one; *redone: JG_NODE_POLL_REDONE
   PollResult node_poll(bool* polled = nullptr, bool* redone = nullptr) {
@@ -492,6 +497,45 @@ class BatchedRaft {
     if (polled) *polled = v.want != 0;
     if (redone) *redone = (v.state & JG_NODE_POLL_REDONE) != 0;
     return r;
+  }
+  // Completions behind a kept node step (jg_step_node_awaited / jg_node_await_view, ABI v23; only callers need a library
+  // that has them): the step registers `a.rows` and then watches, behind its own kernels (and behind the poll `q`, if not
+  // null); node_completions() hands the answer out once step_node_finish has served that step.  The answer is what
+  // await_blocks(a.rows) and watch_completions(a.now_ms, a.limit, a.peek) would have returned between that step and the
+  // next.  The table's room is checked against a bound: what outstanding steps' watches remove counts once they are finished.
+  struct AwaitRequest {
+    std::vector<jg_await_row> rows;
+    uint64_t now_ms = 0;
+    size_t limit = SIZE_MAX;
+    bool peek = false, stats = false;
+  };
+  struct Completions {
+    std::vector<jg_done_row> rows;
+    size_t total = 0;
+    jg_await_stats stats{};  // zero unless wanted
+  };
+  void step_node_awaited(uint64_t now_ms, uint32_t flags, const PollRequest* q, const AwaitRequest& a) {
+    flush_rows();
+    jg_poll p{};
+    if (q) p = polled_words(*q);
+    jg_node_await_request w{};
+    w.rows = a.rows.data(), w.n = a.rows.size();
+    w.flags = a.peek ? (uint32_t)JG_WATCH_PEEK : 0u, w.want_stats = a.stats ? 1u : 0u;
+    w.now_ms = a.now_ms, w.cap = a.limit;
+    check(jg_step_node_awaited(e_, now_ms, flags | (uint32_t)JG_NODE_ASYNC | (uint32_t)JG_NODE_KEEP, q ? &p : nullptr, &w));
+    step_blocks_.emplace_back();
+    step_blocks_.back().swap(pending_blocks_);  // (as step_node_begin)
+  }
+  // the completions of the kept step step_node_finish served last; *attached: that step carried a request; *redone: JG_NODE_POLL_REDONE
+  Completions node_completions(bool* attached = nullptr, bool* redone = nullptr) {
+    jg_node_await v{};
+    check(jg_node_await_view(e_, &v));
+    Completions c;
+    if (v.rows_n) c.rows.assign(v.rows, v.rows + v.rows_n);
+    c.total = v.total, c.stats = v.stats;
+    if (attached) *attached = v.attached != 0;
+    if (redone) *redone = (v.state & JG_NODE_POLL_REDONE) != 0;
+    return c;
   }
   // commit rows as the FSM rows a dense step does not queue: every row that is COMMITTED and not REWOUND becomes
   // JG_FSM_APPLY_LEADER (where LEADS: keys (a, b]) or JG_FSM_APPLY_FOLLOWER (keys [a, b)) {a = commit_from, b = commit}; a
@@ -1025,6 +1069,7 @@ class BatchedEventLoop {
   template <class Raft = BatchedRaft>
   void set_poll(const typename Raft::PollRequest& q, PollSink sink) {
     Raft* const r = &raft_;
+    poll_q_ = std::make_shared<BatchedRaft::PollRequest>(q);
     begin_polled_ = [r, q](uint64_t at, uint32_t flags) {
       typename Raft::PollRequest qq = q;
       if (qq.timed) qq.clock.now_ms = at;
@@ -1034,6 +1079,34 @@ class BatchedEventLoop {
       bool polled = false, redone = false;
       const typename Raft::PollResult res = r->node_poll(&polled, &redone);
       if (polled && sink) sink(res, redone);
+    };
+  }
+
+  // The completion feed of a loop with two ticks in flight (ABI v23; only a caller of set_completions needs a library that
+  // has jg_step_node_awaited / jg_node_await_view): with in_flight >= 2 every tick's step registers the waiters `source`
+  // hands over for it - called when the step begins, with the step's time - and watches at that time; `sink` receives the
+  // done rows when that tick's outputs are consumed, after the poll's sink.  The poll of set_poll, if any, travels with the
+  // same step.  `limit`: the rows a tick takes (what is left is pending at the next).
+  using CompletionSource = std::function<std::vector<jg_await_row>(uint64_t now_ms)>;
+  using CompletionSink = std::function<void(const std::vector<jg_done_row>&, bool redone)>;
+  template <class Raft = BatchedRaft>
+  void set_completions(CompletionSource source, CompletionSink sink, size_t limit = SIZE_MAX) {
+    Raft* const r = &raft_;
+    begin_awaited_ = [this, r, source, limit](uint64_t at, uint32_t flags) {
+      typename Raft::AwaitRequest a;
+      if (source) a.rows = source(at);
+      a.now_ms = at, a.limit = limit;
+      BatchedRaft::PollRequest qq;
+      if (poll_q_) {
+        qq = *poll_q_;
+        if (qq.timed) qq.clock.now_ms = at;
+      }
+      r->step_node_awaited(at, flags, poll_q_ ? &qq : nullptr, a);
+    };
+    view_awaited_ = [r, sink]() {
+      bool attached = false, redone = false;
+      const typename Raft::Completions c = r->node_completions(&attached, &redone);
+      if (attached && sink) sink(c.rows, redone);
     };
   }
 
@@ -1131,10 +1204,13 @@ class BatchedEventLoop {
     if (dense) {
       if (!in_.empty()) raft_.submit_rows(in_.view());
       in_.clear();
-      const bool polled = two && begin_polled_;
-      if (polled) begin_polled_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u));
+      const bool awaited = two && begin_awaited_;  // (the step with both attachments, if there is a poll)
+      const bool polled = two && (begin_polled_ || (awaited && poll_q_));
+      if (awaited) begin_awaited_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u));
+      else if (polled) begin_polled_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u));
       else raft_.step_node_begin(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u), pipelined, two);
       polled_steps_.push_back(polled);
+      awaited_steps_.push_back(awaited);
       answers_of_step_.push_back(std::move(answers));  // (once the step has begun: one entry per open step, whatever begin() throws)
       last_at_ = at;
       if (pipelined) return;
@@ -1158,6 +1234,11 @@ class BatchedEventLoop {
       const bool polled = polled_steps_.front();
       polled_steps_.pop_front();
       if (polled) view_polled_();
+    }
+    if (!awaited_steps_.empty()) {
+      const bool awaited = awaited_steps_.front();
+      awaited_steps_.pop_front();
+      if (awaited) view_awaited_();
     }
   }
   // Address::Local messages (server.rs:143) are applied before anything new is accepted
@@ -1227,6 +1308,10 @@ class BatchedEventLoop {
   std::function<void(uint64_t, uint32_t)> begin_polled_;  // set_poll: the step with the request attached ...
   std::function<void()> view_polled_;                      // ... and its answer to the sink
   std::deque<bool> polled_steps_;                          // per open step: was it begun with the poll
+  std::shared_ptr<BatchedRaft::PollRequest> poll_q_;       // set_poll's request: an awaited step carries it along
+  std::function<void(uint64_t, uint32_t)> begin_awaited_;  // set_completions: the step with the request(s) attached ...
+  std::function<void()> view_awaited_;                     // ... and its done rows to the sink
+  std::deque<bool> awaited_steps_;                         // per open step: was it begun with the completion request
   std::deque<Message> local_;
   std::map<uint64_t, Response> requests_;
   std::map<std::pair<uint32_t, BlockId>, uint64_t> notifications_;
