@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 23u /* v23: jg_step_node_awaited / jg_node_await_view (completions behind a kept node step: the purgatory with two ticks in flight); v22: jg_engine_await_open / jg_engine_await_blocks / jg_engine_watch_completions (the completion feed: fsm::Driver's notifications on the device); v21: jg_step_node_polled / jg_node_poll_view (a poll behind a kept node step: the feeds with two ticks in flight); v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 24u /* v24: jg_engine_await_cancel, jg_node_await_request.cancel_keys / cancel_n / cancel_mask, jg_node_await.marked, JG_DONE_CANCELLED (withdrawing waiters: a closed connection leaves the purgatory); v23: jg_step_node_awaited / jg_node_await_view (completions behind a kept node step: the purgatory with two ticks in flight); v22: jg_engine_await_open / jg_engine_await_blocks / jg_engine_watch_completions (the completion feed: fsm::Driver's notifications on the device); v21: jg_step_node_polled / jg_node_poll_view (a poll behind a kept node step: the feeds with two ticks in flight); v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -757,6 +757,7 @@ int jg_engine_watch_commits(jg_engine* e, uint32_t flags, uint32_t g0, uint32_t 
  * A waiter's VERDICT is decided at a watch, from its slot's state as jg_read_state would return it then -
  * role, fault, JG_FIELD_TERM, JG_FIELD_COMMIT (decoded exactly as the commit feed and the point queries
  * do), JG_FIELD_HEAD.  The first rule that matches wins:
+ *   0. (ABI v24) withdrawn by jg_engine_await_cancel -> JG_DONE_CANCELLED, whatever the slot looks like
  *   1. fault 255 -> JG_DONE_LOST | JG_DONE_VACANT; any other nonzero fault -> JG_DONE_LOST | JG_DONE_FAULTED
  *   2. term != 0 and (role is not leader or JG_FIELD_TERM != term) -> JG_DONE_LOST.  Deliberately BEFORE
  *      the applied test: a block that committed under a later leadership cannot be told from a different
@@ -792,11 +793,15 @@ int jg_engine_watch_commits(jg_engine* e, uint32_t flags, uint32_t g0, uint32_t 
  * delivers into what is left of `cap`, in shard order, `group` the parent's index; a shard behind the
  * point where cap ran out keeps its waiters. */
 enum { JG_DONE_APPLIED = 1u, JG_DONE_LOST = 2u, JG_DONE_EXPIRED = 4u,
-       JG_DONE_VACANT = 8u, JG_DONE_FAULTED = 16u };   /* jg_done_row.state */
+       JG_DONE_VACANT = 8u, JG_DONE_FAULTED = 16u,
+       JG_DONE_CANCELLED = 32u };                      /* jg_done_row.state (CANCELLED: ABI v24) */
+/* jg_await_row.flags as the TABLE keeps it: the waiter was withdrawn by jg_engine_await_cancel.  The table's
+ * own bit - never accepted from a caller: registration refuses any nonzero flags. */
+enum { JG_AWAIT_WITHDRAWN = 1u };
 typedef struct jg_await_row {          /* 48 bytes: three 16-byte pieces */
   uint32_t group;                      /* local slot (a sharded handle: index within the parent) */
-  uint32_t flags;                      /* must be 0 */
-  uint64_t token;                      /* opaque: returned as given */
+  uint32_t flags;                      /* must be 0 (the table keeps JG_AWAIT_WITHDRAWN here) */
+  uint64_t token;                      /* opaque: returned as given (jg_engine_await_cancel matches it under a mask) */
   uint64_t block_id;                   /* != 0 */
   uint64_t term;                       /* 0: the reference's rule; else the leadership the waiter is guarded by */
   uint64_t deadline_ms;                /* 0: never expires */
@@ -812,11 +817,41 @@ typedef struct jg_done_row {           /* 48 bytes: three 16-byte pieces */
 typedef struct jg_await_stats {
   uint64_t waiting, done, applied, lost, expired;   /* before this call's delivery, over every waiter */
   uint64_t left;                                    /* outstanding after the call */
-} jg_await_stats;
+} jg_await_stats;                      /* the verdicts are exclusive: cancelled = done - applied - lost - expired */
 int jg_engine_await_open(jg_engine* e, size_t capacity);
 int jg_engine_await_blocks(jg_engine* e, const jg_await_row* rows, size_t n);
 int jg_engine_watch_completions(jg_engine* e, uint32_t flags, uint64_t now_ms, jg_done_row* out, size_t cap, size_t* total,
                                 jg_await_stats* stats /* may be NULL */);
+
+/* ---- withdrawing waiters: a closed connection leaves the purgatory (ABI v24) ---------------------------
+ * A waiter otherwise leaves the table only applied, lost or expired: a client that hangs up while its
+ * request waits on a healthy leader, unguarded and without a deadline, would sit there for ever (the
+ * reference's notifications map has the same leak: an entry goes only at the Apply that answers it).
+ *
+ * jg_engine_await_cancel MARKS, in place, every outstanding waiter whose (token & mask) is one of the n_keys
+ * keys: mask = ~0 withdraws exact tokens; a caller that keeps a connection id in the token's high 32 bits
+ * withdraws connections with mask = 0xFFFFFFFF00000000 and the ids << 32 as keys; mask = 0 with the single
+ * key 0 withdraws everything (shutdown, or before a resize).  The keys are copied at entry, sorted, and
+ * duplicates removed: any order will do.  *marked = the waiters NEWLY marked by this call (one that was
+ * marked already is not counted again).
+ *
+ * RULE 0 of the verdict, ahead of rule 1: a marked waiter is done with state == JG_DONE_CANCELLED - that
+ * bit alone, whatever its slot looks like (vacant, faulted, deposed, applied, past its deadline).  Everything
+ * else is the feed as it stands: the waiter is delivered as a jg_done_row in registration order, subject to
+ * cap and JG_WATCH_PEEK, with the slot's fields as they are at that watch, exactly once; the mark is stored
+ * in the waiter, so it survives a compaction and a watch whose cap ran out before it.  A cancel removes
+ * nothing: a cancelled waiter counts as outstanding until a watch delivers it.  Waiters registered after
+ * the call are not affected by it.  In jg_await_stats a cancelled waiter counts in `done` and in none of
+ * applied / lost / expired.
+ *
+ * n_keys == 0: JG_OK, 0 marked.  No open table: JG_OK, 0 marked (as a watch).  JG_EINVAL - nothing written,
+ * nothing marked - for a null `e` or `marked`, null `keys` with n_keys > 0, n_keys > JG_AWAIT_CANCEL_MAX, a
+ * key with a bit outside `mask` (it could never match: a caller's bug), and while kept node steps are
+ * outstanding; JG_NODE_ASYNC steps are settled first.  A multi-device parent sends the same keys to every
+ * shard, *marked is the sum.  Reads nothing but the table and writes nothing but the marks: no step, drain,
+ * read or other feed can observe it. */
+#define JG_AWAIT_CANCEL_MAX 65536u
+int jg_engine_await_cancel(jg_engine* e, const uint64_t* keys, size_t n_keys, uint64_t mask, size_t* marked);
 
 /* ---- one poll per tick: the three feeds and the two censuses in one call (ABI v18) --------------------
  * An event loop that consumes several feeds asks them of the same slots once per tick.  Asked separately
@@ -1269,9 +1304,11 @@ int jg_node_poll_view(jg_engine* e, jg_node_poll* out);
  * An AWAITED step carries a registration and a watch with it, as a polled step carries its poll.
  *
  * CONTRACT.  Let S be the engine after kept step t is settled and before anything else touches it.  The
- * answer viewed for step t is what jg_engine_await_blocks(e, rows, n) and then
+ * answer viewed for step t is what jg_engine_await_blocks(e, rows, n), then (ABI v24, cancel_n != 0)
+ * jg_engine_await_cancel(e, cancel_keys, cancel_n, cancel_mask, &marked) and then
  * jg_engine_watch_completions(e, flags, now_ms, out, cap, &total, &stats) leave when called on S: every
- * row byte, total, all six stat words; and the table afterwards holds the same waiters in the same order.
+ * row byte, total, all six stat words, marked; and the table afterwards holds the same waiters in the same
+ * order.  Rows registered by the step can be withdrawn by its own cancel.
  * Consecutive awaited steps are consecutive register-then-watch pairs: what a small cap leaves pending at
  * step t is pending at step t + 1.  A kept step without the attachment leaves the table alone.  The
  * three synchronous calls stay refused while kept steps are outstanding; once none is they may be mixed
@@ -1279,10 +1316,10 @@ int jg_node_poll_view(jg_engine* e, jg_node_poll* out);
  *
  * jg_step_node_awaited with await == NULL is exactly jg_step_node_polled(e, now_ms, flags, poll).
  * Otherwise the polled step's rules hold (JG_NODE_ASYNC | JG_NODE_KEEP, no multi-device parent), *await
- * and its rows are copied at entry, and every argument is checked by the rules of jg_engine_await_blocks
- * and jg_engine_watch_completions - and `poll`, if not NULL, by jg_engine_poll's - before anything of the
- * step is queued: a refused call steps nothing and leaves the submitted rows queued.  The poll, if both
- * are attached, is queued first.
+ * its rows and its cancel keys are copied at entry, and every argument is checked by the rules of
+ * jg_engine_await_blocks, jg_engine_await_cancel and jg_engine_watch_completions - and `poll`, if not
+ * NULL, by jg_engine_poll's - before anything of the step is queued: a refused call steps nothing and
+ * leaves the submitted rows queued.  The poll, if both are attached, is queued first.
  *
  * CAPACITY.  With steps outstanding the host does not know how many waiters the table holds; it keeps a
  * BOUND: the waiters outstanding as of the newest viewed step or synchronous call, plus every row
@@ -1301,6 +1338,9 @@ typedef struct jg_node_await_request {
   uint32_t want_stats;                /* 0 / 1                                                              */
   uint64_t now_ms;                    /* != UINT64_MAX                                                      */
   size_t cap;                         /* rows the caller takes; 0: counts only                              */
+  const uint64_t* cancel_keys;        /* [cancel_n] jg_engine_await_cancel between the two (ABI v24)        */
+  size_t cancel_n;                    /* 0: no cancel                                                       */
+  uint64_t cancel_mask;
 } jg_node_await_request;
 int jg_step_node_awaited(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_poll* poll /* may be NULL */,
                          const jg_node_await_request* await /* may be NULL */);
@@ -1309,6 +1349,7 @@ typedef struct jg_node_await {
   const jg_done_row* rows;            /* [rows_n], registration order; rows_n = min(cap, total)             */
   size_t rows_n, total;
   jg_await_stats stats;               /* zero unless wanted                                                 */
+  size_t marked;                      /* the waiters the step's cancel newly marked (ABI v24)               */
 } jg_node_await;
 int jg_node_await_view(jg_engine* e, jg_node_await* out);
 

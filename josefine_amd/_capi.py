@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -253,7 +253,9 @@ class ReplCensus(C.Structure):
 
 
 # jg_done_row.state
-DONE_APPLIED, DONE_LOST, DONE_EXPIRED, DONE_VACANT, DONE_FAULTED = 1, 2, 4, 8, 16
+DONE_APPLIED, DONE_LOST, DONE_EXPIRED, DONE_VACANT, DONE_FAULTED, DONE_CANCELLED = 1, 2, 4, 8, 16, 32
+AWAIT_WITHDRAWN = 1  # jg_await_row.flags as the table keeps it (never accepted from a caller)
+AWAIT_CANCEL_MAX = 65536  # jg_engine_await_cancel: the most keys of one call
 
 
 class AwaitStats(C.Structure):
@@ -291,13 +293,13 @@ class NodePoll(C.Structure):
 class NodeAwaitRequest(C.Structure):
     """jg_node_await_request."""
     _fields_ = [("rows", C.c_void_p), ("n", C.c_size_t), ("flags", C.c_uint32), ("want_stats", C.c_uint32), ("now_ms", C.c_uint64),
-                ("cap", C.c_size_t)]
+                ("cap", C.c_size_t), ("cancel_keys", C.c_void_p), ("cancel_n", C.c_size_t), ("cancel_mask", C.c_uint64)]
 
 
 class NodeAwait(C.Structure):
     """jg_node_await."""
     _fields_ = [("attached", C.c_uint32), ("state", C.c_uint32), ("rows", C.c_void_p), ("rows_n", C.c_size_t), ("total", C.c_size_t),
-                ("stats", AwaitStats)]
+                ("stats", AwaitStats), ("marked", C.c_size_t)]
 
 
 # mailbox words (josefine_gpu.h: JG_ANSWER / JG_AE)
@@ -444,6 +446,7 @@ class Api:
         "engine_await_blocks": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
         "engine_watch_completions": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                                C.POINTER(AwaitStats)]),
+        "engine_await_cancel": (C.c_int, [_P, C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_size_t)]),
         "engine_poll": (C.c_int, [_P, C.POINTER(Poll)]),
         "step_node_polled": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.POINTER(Poll)]),
         "node_poll_view": (C.c_int, [_P, C.POINTER(NodePoll)]),
@@ -501,4 +504,5 @@ HEADER_SYMBOLS = [
     "jg_engine_watch_replicas_timed",
     "jg_engine_await_open", "jg_engine_await_blocks", "jg_engine_watch_completions",
     "jg_step_node_awaited", "jg_node_await_view",
+    "jg_engine_await_cancel",
 ]

@@ -1,7 +1,7 @@
-// jg_api_await.h - jg_engine_await_open / jg_engine_await_blocks / jg_engine_watch_completions: the completion feed
-// (jg_await.h).  Calls that read, under the rules of jg_api_manage.h: refused while kept node steps are outstanding,
-// JG_NODE_ASYNC steps settled, the rows' landing area carved from the engine's staging, a multi-device handle served shard
-// by shard.  A watch queues its passes back to back and synchronises once; a registration is one host-to-device copy
+// jg_api_await.h - jg_engine_await_open / jg_engine_await_blocks / jg_engine_await_cancel / jg_engine_watch_completions: the
+// completion feed (jg_await.h).  Calls that read, under the rules of jg_api_manage.h: refused while kept node steps are
+// outstanding, JG_NODE_ASYNC steps settled, the rows' landing area carved from the engine's staging, a multi-device handle
+// served shard by shard.  A watch queues its passes back to back and synchronises once; a registration is one host-to-device copy
 // behind the table's end.  The feed walks a table, not a slot range, so it keeps a chain of its own (await_shard) beside
 // the other feeds' one host path (jg_api_poll.h), in the same three pieces: await_plan hands out the geometry and the
 // sections of one block, await_bind the arguments over whoever's block it is, await_queue the chain.  The synchronous watch
@@ -13,9 +13,10 @@
 namespace {
 
 // offsets in AwaitTable::misc
-constexpr size_t AWT_O_TOTAL = 0, AWT_O_SUM = 16, AWT_O_JOB = 64, AWT_O_HEAD = 128, AWT_MISC_BYTES = 144;
+constexpr size_t AWT_O_TOTAL = 0, AWT_O_SUM = 16, AWT_O_JOB = 64, AWT_O_HEAD = 128, AWT_O_MARKED = 144, AWT_MISC_BYTES = 160;
 static_assert(AWT_O_SUM + JG_AWT_WORDS * 8 <= AWT_O_JOB && AWT_O_JOB + sizeof(JgScanJob) <= AWT_O_HEAD, "AwaitTable::misc");
-static_assert(AWT_O_HEAD % 16 == 0 && AWT_O_HEAD + sizeof(JgAwaitHead) <= AWT_MISC_BYTES, "AwaitTable::misc: the head");
+static_assert(AWT_O_HEAD % 16 == 0 && AWT_O_HEAD + sizeof(JgAwaitHead) <= AWT_O_MARKED, "AwaitTable::misc: the head");
+static_assert(AWT_O_MARKED + 8 <= AWT_MISC_BYTES, "AwaitTable::misc: the marked count");
 // (a waiter's index, and the tile count, are 32-bit in the kernels)
 constexpr size_t AWT_MAX_CAPACITY = 0xFFFF0000ull;
 
@@ -36,6 +37,7 @@ int await_open_shard(jg_engine* e, size_t capacity) {
   get(&t.verdict, capacity);
   get(&t.bsum, tiles * 8);
   get(&t.part, (size_t)JG_AWT_PARTS * JG_AWT_WORDS * 8);
+  get(&t.mpart, (size_t)JG_AWT_PARTS * 8);  // (the mark pass's own: the count pass of the same chain overwrites `part`)
   get(&t.misc, AWT_MISC_BYTES);
   if (rc) {
     t.release();
@@ -63,24 +65,26 @@ struct AwaitPlan {
   bool kept = false;
   uint32_t n = 0, tiles = 0, parts = 0;  // the waiters the passes are launched for
   size_t m = 0, wcap = 0;                // staged rows (kept); rows the landing area holds
+  size_t ck = 0;                         // the cancel's keys (kept: staged behind the rows)
   Carve c;
-  size_t o_out = 0, o_rows = 0, o_hdr = 0;
+  size_t o_out = 0, o_rows = 0, o_hdr = 0, o_keys = 0;
   JgAwaitArgs a{};
   JgAwaitKeptArgs k{};
 };
 
-void await_plan(AwaitPlan& P, bool kept, size_t n, size_t m, size_t cap) {
-  P.kept = kept, P.n = (uint32_t)n, P.m = m;
+void await_plan(AwaitPlan& P, bool kept, size_t n, size_t m, size_t cap, size_t ck = 0) {
+  P.kept = kept, P.n = (uint32_t)n, P.m = m, P.ck = ck;
   P.tiles = std::max<uint32_t>((P.n + JG_AWT_TILE - 1) / JG_AWT_TILE, kept ? 1u : 0u);  // (an awaited step's header wants its total: one tile at least)
   P.parts = std::min<uint32_t>(P.tiles, JG_AWT_PARTS);
   P.wcap = std::min<size_t>(cap, n);
   P.o_out = P.c.sect(P.wcap * sizeof(jg_done_row));
-  if (kept) P.o_rows = P.c.sect(m * sizeof(jg_await_row)), P.o_hdr = P.c.sect(JG_AH_WORDS * 8);
+  if (kept) P.o_rows = P.c.sect(m * sizeof(jg_await_row)), P.o_hdr = P.c.sect(JG_AH_WORDS * 8), P.o_keys = P.c.sect(ck * 8);
 }
 
 // the arguments of every pass over block B; `gate`: null, or the device word that makes an awaited step's chain leave
 // everything alone (jg_await.h)
-void await_bind(jg_engine* e, AwaitPlan& P, char* B, bool peek, bool stats, uint64_t now_ms, uint32_t add, const uint32_t* gate) {
+void await_bind(jg_engine* e, AwaitPlan& P, char* B, bool peek, bool stats, uint64_t now_ms, uint32_t add, const uint32_t* gate,
+                uint64_t cmask = 0) {
   jg_engine::AwaitTable& t = e->await;
   if (!P.kept) {
     JgAwaitArgs& a = P.a;
@@ -98,10 +102,11 @@ void await_bind(jg_engine* e, AwaitPlan& P, char* B, bool peek, bool stats, uint
   k.rows = (const uint4*)(B + P.o_rows), k.buf[0] = t.buf[0], k.buf[1] = t.buf[1], k.verdict = t.verdict;
   k.bsum = t.bsum, k.part = t.part, k.total = (const uint64_t*)(t.misc + AWT_O_TOTAL);
   k.out = (uint4*)(B + P.o_out), k.hdr = (uint64_t*)(B + P.o_hdr);
+  k.keys = (const uint64_t*)(B + P.o_keys), k.mpart = t.mpart, k.mask = cmask, k.n_keys = (uint32_t)P.ck;
 }
 
-// the whole chain on the engine's stream (`job`: where the device reads the scan job): [the append,] the count pass, the
-// scan, the stats sum if wanted, the write pass - queued unseen: with nothing done every workgroup returns after its first
+// the whole chain on the engine's stream (`job`: where the device reads the scan job): [the append, the mark pass,] the
+// count pass, the scan, the stats sum if wanted, the write pass - queued unseen: with nothing done every workgroup returns after its first
 // loads - [and the header kernel, which folds the stats itself]
 int await_queue(jg_engine* e, const AwaitPlan& P, const JgScanJob* job, bool stats) {
   jg_engine::AwaitTable& t = e->await;
@@ -122,6 +127,10 @@ int await_queue(jg_engine* e, const AwaitPlan& P, const JgScanJob* job, bool sta
   } else {
     if (P.m) {
       hipLaunchKernelGGL(k_await_append, dim3((uint32_t)((P.m * 3 + JG_BLOCK - 1) / JG_BLOCK)), block, 0, e->stream, P.k);
+      e->n_launch++;
+    }
+    if (P.ck) {  // (behind the append: the step's own rows can be withdrawn by it)
+      hipLaunchKernelGGL(k_await_mark_kept, dim3(P.parts), block, 0, e->stream, P.k);
       e->n_launch++;
     }
     hipLaunchKernelGGL(k_await_count_kept, dim3(P.parts), block, 0, e->stream, e->dev, P.k);
@@ -169,6 +178,46 @@ int await_shard(jg_engine* e, uint32_t flags, uint64_t now_ms, uint32_t add, jg_
   return JG_OK;
 }
 
+// one single-device engine's part of a cancel: the mark pass over its table and the reduce, the keys (sorted, distinct,
+// within mask: await_keys_check) staged into the engine's staging; *marked the waiters newly marked.  The caller has settled
+// the engine's JG_NODE_ASYNC step
+int await_cancel_shard(jg_engine* e, const std::vector<uint64_t>& keys, uint64_t mask, size_t* marked) {
+  *marked = 0;
+  HIPCHK(hipSetDevice(e->device));
+  jg_engine::AwaitTable& t = e->await;
+  if (!t.n) return JG_OK;
+  Carve c;
+  c.sect(keys.size() * 8);
+  char* B = nullptr;
+  if (const int rc = c.on_staging(e, B)) return rc;
+  JgAwaitMarkArgs a{};
+  a.n = (uint32_t)t.n, a.tiles = (a.n + JG_AWT_TILE - 1) / JG_AWT_TILE, a.parts = std::min<uint32_t>(a.tiles, JG_AWT_PARTS);
+  a.n_keys = (uint32_t)keys.size(), a.mask = mask;
+  a.tab = t.buf[t.cur], a.keys = (const uint64_t*)B, a.part = t.mpart, a.sum = (uint64_t*)(t.misc + AWT_O_MARKED);
+  HIPCHK(hipMemcpyAsync(B, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_await_mark, dim3(a.parts), dim3(JG_BLOCK), 0, e->stream, a);
+  hipLaunchKernelGGL(k_await_mark_sum, dim3(1), dim3(JG_BLOCK), 0, e->stream, a);
+  e->n_launch += 2;
+  HIPCHK(hipGetLastError());
+  uint64_t got = 0;
+  HIPCHK(hipMemcpyAsync(&got, a.sum, 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  *marked = (size_t)got;
+  return JG_OK;
+}
+
+// the rules of jg_engine_await_cancel for a key set; `out`: the keys copied, sorted, duplicates removed
+int await_keys_check(const uint64_t* keys, size_t n, uint64_t mask, const char* who, std::vector<uint64_t>& out) {
+  if (n && !keys) return fail(JG_EINVAL, "null argument");
+  if (n > JG_AWAIT_CANCEL_MAX) return fail(JG_EINVAL, std::string(who) + ": more than JG_AWAIT_CANCEL_MAX keys");
+  for (size_t i = 0; i < n; i++)
+    if (keys[i] & ~mask) return fail(JG_EINVAL, std::string(who) + ": a key has a bit outside the mask (it could never match)");
+  out.assign(keys, keys + n);
+  std::sort(out.begin(), out.end());
+  out.erase(std::unique(out.begin(), out.end()), out.end());
+  return JG_OK;
+}
+
 // the rules of jg_engine_await_blocks for rows that are about to be registered on a single-device engine
 int await_rows_check(const jg_engine* e, const jg_await_row* rows, size_t n, const char* who) {
   auto refuse = [&](const char* what) { return fail(JG_EINVAL, std::string(who) + ": " + what); };
@@ -195,13 +244,15 @@ size_t node_await_bound(const jg_engine* e) {
   return b;
 }
 
-// the step's rows into the set's pinned memory (the set is the step's from here on; whatever read it last has been viewed)
-int node_await_stage(jg_engine::NodeOut& o, const jg_await_row* rows) {
-  const size_t bytes = o.aw.m * sizeof(jg_await_row);
+// the step's rows, and behind them its cancel keys, into the set's pinned memory (the set is the step's from here on;
+// whatever read it last has been viewed)
+int node_await_stage(jg_engine::NodeOut& o, const jg_await_row* rows, const uint64_t* keys) {
+  const size_t bytes = o.aw.m * sizeof(jg_await_row), kbytes = o.aw.ck * 8;
   o.l_await_up.n = 0;
-  if (!bytes) return JG_OK;
-  HIPCHK(o.l_await_up.reserve(bytes));
-  std::memcpy(o.l_await_up.p, rows, bytes);
+  if (!(bytes + kbytes)) return JG_OK;
+  HIPCHK(o.l_await_up.reserve(bytes + kbytes));
+  if (bytes) std::memcpy(o.l_await_up.p, rows, bytes);
+  if (kbytes) std::memcpy(o.l_await_up.p + bytes, keys, kbytes);
   return JG_OK;
 }
 
@@ -215,16 +266,17 @@ int node_await_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate) {
   jg_engine::NodeAwait& aw = o.aw;
   jg_engine::AwaitTable& t = e->await;
   AwaitPlan P;
-  await_plan(P, true, aw.bound, aw.m, aw.cap);
+  await_plan(P, true, aw.bound, aw.m, aw.cap, aw.ck);
   if (!aw.scratch) HIPCHK(e->arenas[o.arena].alloc(P.c.at, (void**)&aw.scratch));  // (the pass behind the catch-up pass: the same block)
   if (!o.h_await) {
     HIPCHK(hipHostMalloc((void**)&o.h_await, NODE_AWAIT_PINNED_WORDS * 8, hipHostMallocDefault));
     std::memset(o.h_await, 0, NODE_AWAIT_PINNED_WORDS * 8);
   }
   char* const B = aw.scratch;
-  await_bind(e, P, B, aw.peek, aw.stats, aw.now_ms, 0, gate);
+  await_bind(e, P, B, aw.peek, aw.stats, aw.now_ms, 0, gate, aw.cmask);
   if (!aw.redone) {
     if (aw.m) HIPCHK(hipMemcpyAsync(B + P.o_rows, o.l_await_up.p, aw.m * sizeof(jg_await_row), hipMemcpyHostToDevice, e->stream));
+    if (aw.ck) HIPCHK(hipMemcpyAsync(B + P.o_keys, o.l_await_up.p + aw.m * sizeof(jg_await_row), aw.ck * 8, hipMemcpyHostToDevice, e->stream));
     const jg_engine::NodeOut& other = nd.sets[(&o - nd.sets) ^ 1];
     if (!(other.out && other.aw.on)) {  // (the step before, if it is outstanding and awaited, leaves the head behind its chain)
       JgAwaitHead* const h = (JgAwaitHead*)(o.h_await + NODE_AWAIT_HEAD);
@@ -262,7 +314,7 @@ int node_await_finish(jg_engine* e, jg_engine::NodeOut& o) {
   const uint64_t* const h = o.h_await + NODE_AWAIT_HDR;
   if (h[JG_AH_GATE]) return fail(JG_EDEVICE, "internal: an awaited step's chain was gated and not queued again");
   AwaitPlan P;
-  await_plan(P, true, aw.bound, aw.m, aw.cap);
+  await_plan(P, true, aw.bound, aw.m, aw.cap, aw.ck);
   const size_t given = (size_t)h[JG_AH_GIVEN];
   if (given > P.wcap || h[JG_AH_N] > t.cap) return fail(JG_EDEVICE, "internal: an awaited step's header block is out of range");
   if (given > aw.copied) {
@@ -276,7 +328,7 @@ int node_await_finish(jg_engine* e, jg_engine::NodeOut& o) {
   t.n = (size_t)h[JG_AH_N], t.cur = (int)(h[JG_AH_CUR] & 1u);
   v.attached = 1u, v.state = aw.redone ? (uint32_t)JG_NODE_POLL_REDONE : 0u;
   v.rows = given ? (const jg_done_row*)o.l_await.p : nullptr;
-  v.rows_n = given, v.total = (size_t)h[JG_AH_TOTAL];
+  v.rows_n = given, v.total = (size_t)h[JG_AH_TOTAL], v.marked = (size_t)h[JG_AH_MARKED];
   if (aw.stats) {  // (jg_await_stats is the stat words in order, then left: jg_await.h)
     std::memcpy(&v.stats, h + JG_AH_STATS, JG_AWT_WORDS * 8);
     v.stats.left = h[JG_AH_LEFT];
@@ -329,6 +381,31 @@ int jg_engine_await_blocks(jg_engine* e, const jg_await_row* rows, size_t n) {
     if (const int rc = node_settle(s)) return rc;
     return await_append_shard(s, part[d].data(), part[d].size());
   });
+}
+
+int jg_engine_await_cancel(jg_engine* e, const uint64_t* keys, size_t n_keys, uint64_t mask, size_t* marked) {
+  if (!e || !marked) return fail(JG_EINVAL, "null argument");
+  std::vector<uint64_t> sorted;
+  if (const int rc = await_keys_check(keys, n_keys, mask, "jg_engine_await_cancel", sorted)) return rc;
+  if (const int rc = refuse_first(e, kept_refuse)) return rc;
+  {  // JG_NODE_ASYNC steps are settled first, whatever the call then finds to do
+    const int rc = each_shard(e, [&](size_t d) -> int {
+      jg_engine* s = shard_at(e, d);
+      HIPCHK(hipSetDevice(s->device));
+      return node_settle(s);
+    });
+    if (rc) return rc;
+  }
+  const size_t D = shard_count(e);
+  std::vector<size_t> got(D, 0);
+  if (!sorted.empty() && shard_at(e, 0)->await.cap) {
+    const int rc = each_shard(e, [&](size_t d) -> int { return await_cancel_shard(shard_at(e, d), sorted, mask, &got[d]); });
+    if (rc) return rc;
+  }
+  size_t sum = 0;
+  for (size_t d = 0; d < D; d++) sum += got[d];
+  *marked = sum;
+  return JG_OK;
 }
 
 int jg_engine_watch_completions(jg_engine* e, uint32_t flags, uint64_t now_ms, jg_done_row* out, size_t cap, size_t* total,

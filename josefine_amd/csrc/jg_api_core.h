@@ -335,20 +335,21 @@ struct jg_engine {
   uint4* commit_shadow = nullptr;
   // jg_engine_await_open: the completion feed's table (jg_await.h) - two buffers of `cap` waiters, of which buf[cur] holds
   // the n outstanding ones in registration order, a verdict byte per waiter, the tile counts / prefixes, the partial stat
-  // records and one block for the total, the stats, the scan job and the table's HEAD on the device ({n, cur}: what the
+  // records (and the mark pass's own: jg_engine_await_cancel) and one block for the total, the stats, the scan job, the
+  // marked count and the table's HEAD on the device ({n, cur}: what the
   // chain of an awaited node step reads and its header kernel writes).  n and cur are authoritative while no awaited step
   // is outstanding; while one is, the device's head is, and they are refreshed from the header block at every view
   struct AwaitTable {
     uint4* buf[2] = {nullptr, nullptr};
     uint8_t* verdict = nullptr;
-    uint64_t *bsum = nullptr, *part = nullptr;
+    uint64_t *bsum = nullptr, *part = nullptr, *mpart = nullptr;
     char* misc = nullptr;
     size_t cap = 0, n = 0;
     int cur = 0;
     void release() {
-      for (void* p : {(void*)buf[0], (void*)buf[1], (void*)verdict, (void*)bsum, (void*)part, (void*)misc})
+      for (void* p : {(void*)buf[0], (void*)buf[1], (void*)verdict, (void*)bsum, (void*)part, (void*)mpart, (void*)misc})
         if (p) (void)hipFree(p);
-      buf[0] = buf[1] = nullptr, verdict = nullptr, bsum = part = nullptr, misc = nullptr;
+      buf[0] = buf[1] = nullptr, verdict = nullptr, bsum = part = mpart = nullptr, misc = nullptr;
       cap = n = 0, cur = 0;
     }
   } await;
@@ -444,6 +445,8 @@ struct jg_engine {
   struct NodeAwait {
     bool on = false;                   // the step carries a request
     size_t m = 0;                      // rows registered first (staged in NodeOut::l_await_up)
+    size_t ck = 0;                     // the cancel's keys: sorted, distinct, staged behind the rows (0: no cancel)
+    uint64_t cmask = 0;
     bool peek = false, stats = false;
     uint64_t now_ms = 0;
     size_t cap = 0;
@@ -492,7 +495,7 @@ struct jg_engine {
     // -- jg_step_node_awaited: the completion request that travels with the step (jg_api_await.h) --------------------------
     NodeAwait aw;                      // the request as copied at entry (on == false: the step carries none)
     uint64_t* h_await = nullptr;       // pinned: the scan job and the head the device reads, then where the header block lands
-    PinnedQueue<char> l_await_up;      // pinned: the step's staged rows on their way up (bytes)
+    PinnedQueue<char> l_await_up;      // pinned: the step's staged rows, then its cancel keys, on their way up (bytes)
     PinnedQueue<char> l_await;         // pinned: where the done rows land (bytes); the first aw.copied rows came with the step
     jg_node_await await_view{};        // what jg_node_await_view hands out once the step's outbox has been viewed
   };

@@ -109,7 +109,7 @@ int node_poll_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate);
 int node_poll_finish(jg_engine* e, jg_engine::NodeOut& o);
 // (jg_api_await.h) the completion request that travels with a kept step: staged at entry, queued behind its kernels (and its
 // poll), collected when its outbox is viewed
-int node_await_stage(jg_engine::NodeOut& o, const jg_await_row* rows);
+int node_await_stage(jg_engine::NodeOut& o, const jg_await_row* rows, const uint64_t* keys);
 int node_await_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate);
 int node_await_finish(jg_engine* e, jg_engine::NodeOut& o);
 
@@ -421,9 +421,10 @@ int node_publish(jg_engine* e, const NodeRun& s, uint32_t seq0, NodeClaim& claim
 }
 
 // `poll`: the request of a polled step (jg_step_node_polled: checked, and a kept step's), or null; `await`: the completion
-// request of an awaited step (jg_step_node_awaited: checked, its bound taken) and the rows it registers, or null
+// request of an awaited step (jg_step_node_awaited: checked, its bound taken), the rows it registers and the keys it cancels
+// (aw.ck of them: sorted, distinct), or null
 int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::NodePoll* poll, const jg_engine::NodeAwait* await,
-              const jg_await_row* await_rows) {
+              const jg_await_row* await_rows, const uint64_t* await_keys) {
   static const bool trace = std::getenv("JG_TRACE_NODE") != nullptr;
   jg_engine::NodeStep& nd = e->node;
   NodeRun s;
@@ -441,7 +442,7 @@ int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::No
   if (nd.poll_viewed == (int)nd.newest) nd.poll_viewed = -1;  // (the answer viewed last lived in this set)
   o.poll = poll ? *poll : jg_engine::NodePoll{};
   o.aw = await ? *await : jg_engine::NodeAwait{};
-  if (o.aw.on && (rc = node_await_stage(o, await_rows))) return rc;  // (the rows are the caller's until here)
+  if (o.aw.on && (rc = node_await_stage(o, await_rows, await_keys))) return rc;  // (the rows are the caller's until here)
   if (s.keep) {  // (the set starts empty: its last step's regions went with that step's arena)
     o.set = e->cur_set, o.arena = e->cur_arena, o.irr_gen = e->irr_gen;
     o.d_fsm_cnt = nullptr, o.d_fsm = o.d_stage = nullptr, o.d_bsum = nullptr;

@@ -487,7 +487,8 @@ int jg_step_node_awaited(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg
     return fail(JG_EINVAL, std::string(who) + ": a poll and a completion request travel with a kept step: JG_NODE_ASYNC | JG_NODE_KEEP");
   if (request)
     if (const int rc = poll_check(e, request, false)) return rc;
-  jg_engine::NodeAwait aw;  // (*await: copied here; its rows once the step has its set - node_await_stage)
+  jg_engine::NodeAwait aw;  // (*await: copied here; its rows and keys once the step has its set - node_await_stage)
+  std::vector<uint64_t> keys;  // (the cancel's keys: copied, sorted, distinct)
   if (await) {
     if (await->n && !await->rows) return fail(JG_EINVAL, "null argument");
     if (!e->await.cap) return fail(JG_EINVAL, "jg_step_node_awaited: no open table (jg_engine_await_open)");
@@ -500,6 +501,8 @@ int jg_step_node_awaited(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg
       return fail(JG_ECAPACITY, "jg_step_node_awaited: the table is full (by the bound: the outstanding steps' watches have not been viewed)");
     aw.on = true, aw.m = await->n, aw.peek = (await->flags & JG_WATCH_PEEK) != 0, aw.stats = await->want_stats != 0;
     aw.now_ms = await->now_ms, aw.cap = await->cap, aw.bound = bound + await->n;
+    if (const int rc = await_keys_check(await->cancel_keys, await->cancel_n, await->cancel_mask, who, keys)) return rc;
+    aw.ck = keys.size(), aw.cmask = await->cancel_mask;
   }
   if (e->inflight.phase) return fail(JG_EINVAL, "a drain is in transfer: jg_drain_wait first");
   jg_engine::NodePoll np;  // (*request and *request->clock: copied here)
@@ -515,7 +518,7 @@ int jg_step_node_awaited(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg
     if (np.timed) np.clk = *request->clock;
     np.pol = request->policy, np.lag_limit = request->census_lag_limit;
   }
-  return node_step(e, now_ms, flags, request ? &np : nullptr, await ? &aw : nullptr, await ? await->rows : nullptr);
+  return node_step(e, now_ms, flags, request ? &np : nullptr, await ? &aw : nullptr, await ? await->rows : nullptr, keys.data());
 }
 
 int jg_node_await_view(jg_engine* e, jg_node_await* out) {

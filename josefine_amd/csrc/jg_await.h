@@ -21,8 +21,15 @@
 //                      serves both ranks.  Nothing to deliver (the total is 0, or cap is): every workgroup returns after
 //                      its first load
 //
+//   k_await_mark       jg_engine_await_cancel (ABI v24): one lane per waiter over piece 0 only - `token & mask` searched in
+//                      the call's sorted keys (in LDS up to JG_AWT_KEYS_LDS of them, else in device memory), a match that
+//                      is not marked yet gets JG_AWAIT_WITHDRAWN into its flag word, in place: the one store to the table
+//                      (4 bytes).  The newly marked counted by ballots into one partial per workgroup, folded by
+//                      k_await_mark_sum.  A marked waiter's verdict is JG_DONE_CANCELLED whatever its slot looks like
+//                      (rule 0 of jg_await_verdict); it leaves at the next watch as every done waiter does
+//
 // No atomics, no scratch.  Nothing here writes a column of the state machine: the only stores are the verdict bytes, the
-// tile counts, the partial records, the rows and the other buffer.
+// tile counts, the partial records, the rows, the other buffer and the marks.
 #pragma once
 #include "jg_device.h"
 #include "jg_lookup.h"  // jg_u32x4
@@ -59,15 +66,17 @@ struct JgAwaitArgs {
 
 __device__ __forceinline__ uint64_t jg_awt_u64(uint32_t lo, uint32_t hi) { return (uint64_t)lo | (uint64_t)hi << 32; }
 
-// The verdict of a waiter (block_id, term, deadline) on a slot in (role, fault, term_now, commit): the first rule wins.
+// The verdict of a waiter (flags, block_id, term, deadline) on a slot in (role, fault, term_now, commit): the first rule wins.
+//   0. withdrawn (jg_engine_await_cancel marked it) -> CANCELLED, whatever the slot looks like
 //   1. vacant -> LOST | VACANT; any other fault -> LOST | FAULTED
 //   2. a guarded waiter (term != 0) whose slot is not the leader of that term any more -> LOST.  Before the applied test on
 //      purpose: a block that committed under a later leadership cannot be told from a different block with the same id
 //   3. applied - the two key conventions of the commit feed from genesis: a leader's Apply keys are (.., commit], a
 //      follower's [.., commit)
 //   4. past its deadline -> EXPIRED
-__device__ __forceinline__ uint32_t jg_await_verdict(uint32_t role, uint32_t fault, uint64_t term_now, uint64_t commit, uint64_t block_id,
-                                                     uint64_t term, uint64_t deadline, uint64_t now) {
+__device__ __forceinline__ uint32_t jg_await_verdict(uint32_t wflags, uint32_t role, uint32_t fault, uint64_t term_now, uint64_t commit,
+                                                     uint64_t block_id, uint64_t term, uint64_t deadline, uint64_t now) {
+  if (wflags & JG_AWAIT_WITHDRAWN) return JG_DONE_CANCELLED;
   if (fault == JG_FAULT_VACANT) return JG_DONE_LOST | JG_DONE_VACANT;
   if (fault) return JG_DONE_LOST | JG_DONE_FAULTED;
   const bool leads = role == JG_ROLE_LEADER;
@@ -92,7 +101,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_await_count(JgDev d, JgAwaitArgs a
     // (the loads stay up there: without an unconditional use the compiler sinks one behind the branch on the role)
     asm volatile("" ::"v"(f), "v"(term_now), "v"(head), "v"(pw), "v"(col), "v"(run_hi));
     const uint32_t role = f & JGF_ROLE_MASK, fault = (f & JGF_FAULT_MASK) >> JGF_FAULT_SHIFT;
-    const uint32_t v = in ? jg_await_verdict(role, fault, term_now, commit, jg_awt_u64(w1.x, w1.y), jg_awt_u64(w1.z, w1.w),
+    const uint32_t v = in ? jg_await_verdict(w0.y, role, fault, term_now, commit, jg_awt_u64(w1.x, w1.y), jg_awt_u64(w1.z, w1.w),
                                              jg_awt_u64(w2.x, w2.y), a.now)
                           : 0u;
     if (in) a.verdict[i] = (uint8_t)v;
@@ -147,6 +156,68 @@ __global__ __launch_bounds__(JG_BLOCK) void k_await_write(JgDev d, JgAwaitArgs a
   out[2] = jg_u32x4{lo(commit), hi(commit), lo(head), hi(head)};
 }
 
+// ---- withdrawing waiters (jg_engine_await_cancel) ---------------------------------------------------------------------------
+#define JG_AWT_KEYS_LDS 2048u  // the keys a workgroup stages into LDS (16 KB); more are searched in device memory (L2)
+
+// key among the sorted, distinct keys[0 .. n)?  (a lower bound by halving: at most 17 probes for JG_AWAIT_CANCEL_MAX keys)
+__device__ __forceinline__ bool jg_awt_has_key(const uint64_t* keys, uint32_t n, uint64_t key) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (keys[mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n && keys[lo] == key;
+}
+
+// The mark pass over tab[0 .. n): the workgroup takes the tiles b, b + parts, ... (< tiles; a tile wholly beyond n ends it),
+// one lane per waiter, piece 0 only.  A waiter whose token & mask is among the keys and that is not marked yet gets the mark
+// into its flag word - a 4-byte store, the only one to the table.  part[b] = the waiters this workgroup marked.
+__device__ __forceinline__ void jg_await_mark_tiles(uint4* tab, uint32_t n, uint32_t tiles, uint32_t parts, const uint64_t* keys, uint32_t n_keys,
+                                                    uint64_t mask, uint64_t* part) {
+  __shared__ uint64_t lds_keys[JG_AWT_KEYS_LDS];
+  const bool staged = n_keys <= JG_AWT_KEYS_LDS;  // (uniform over the launch)
+  if (staged) {  // once, before the first tile: consecutive lanes, consecutive keys
+    for (uint32_t k = threadIdx.x; k < n_keys; k += JG_BLOCK) lds_keys[k] = keys[k];
+    __syncthreads();
+  }
+  uint32_t marked = 0;  // wave-uniform (every lane adds the same popcount)
+  for (uint32_t tile = blockIdx.x; tile < tiles; tile += parts) {  // (uniform over the workgroup)
+    if ((uint64_t)tile * JG_AWT_TILE >= n) break;
+    const uint32_t i = tile * JG_AWT_TILE + threadIdx.x;
+    const bool in = i < n;
+    const size_t at = (size_t)(in ? i : 0u) * 3;
+    const uint4 w0 = tab[at];
+    const uint64_t key = jg_awt_u64(w0.z, w0.w) & mask;
+    const bool has = staged ? jg_awt_has_key(lds_keys, n_keys, key) : jg_awt_has_key(keys, n_keys, key);
+    const bool hit = in && has && !(w0.y & JG_AWAIT_WITHDRAWN);
+    if (hit) ((uint32_t*)(tab + at))[1] = w0.y | JG_AWAIT_WITHDRAWN;
+    marked += __popcll(__ballot(hit));
+  }
+  const uint64_t vals[1] = {marked};
+  jg_block_words<1>(vals, JgNeverMax(), part);
+}
+
+struct JgAwaitMarkArgs {
+  uint32_t n;       // waiters outstanding: the table is tab[0 .. n)
+  uint32_t tiles;   // tiles of JG_AWT_TILE waiters
+  uint32_t parts;   // workgroups (<= JG_AWT_PARTS)
+  uint32_t n_keys;  // <= JG_AWAIT_CANCEL_MAX
+  uint64_t mask;
+  uint4* tab;            // [n][3] the waiters
+  const uint64_t* keys;  // [n_keys] sorted, distinct, every one within mask (device)
+  uint64_t* part;        // [parts] the waiters each workgroup marked
+  uint64_t* sum;         // [1] the waiters the call marked
+};
+
+__global__ __launch_bounds__(JG_BLOCK) void k_await_mark(JgAwaitMarkArgs a) {
+  jg_await_mark_tiles(a.tab, a.n, a.tiles, a.parts, a.keys, a.n_keys, a.mask, a.part);
+}
+
+__global__ __launch_bounds__(JG_BLOCK) void k_await_mark_sum(JgAwaitMarkArgs a) {
+  jg_parts_reduce<1>(a.part, a.parts, a.sum, JgNeverMax());
+}
+
 // ---- the feed behind a kept node step (jg_step_node_awaited) --------------------------------------------------------------
 // With kept steps outstanding the host knows neither how many waiters the table holds nor which buffer holds them: both are
 // the outcome of watches whose totals have not come home.  So the table has a HEAD on the device, {n, cur}, and the chain
@@ -154,9 +225,12 @@ __global__ __launch_bounds__(JG_BLOCK) void k_await_write(JgDev d, JgAwaitArgs a
 //
 //   k_await_append      the step's m staged rows (its arena's, uploaded behind the step) to buf[cur] + n * 3: one 16-byte
 //                       piece a lane, consecutive lanes consecutive pieces; the head read once per workgroup, never written
+//   k_await_mark_kept   (the step carries a cancel) the mark pass over n_eff = head.n + m waiters of buf[head.cur]: rows the
+//                       same step registered can be withdrawn by it
 //   k_await_count_kept  k_await_count over n_eff = head.n + m waiters of buf[head.cur], launched for the host's BOUND on
 //   k_await_write_kept  n_eff (`tiles`); a tile wholly beyond n_eff counts 0 / returns, so the one scan over `tiles` holds
-//   k_await_header      one workgroup behind them: the partial stat records folded (k_await_stats_sum's job), the answer but
+//   k_await_header      one workgroup behind them: the partial stat records folded (k_await_stats_sum's job) and the mark
+//                       pass's partials (k_await_mark_sum's), the answer but
 //                       the rows as ONE block - and then, alone of the chain, the head: n = n_eff - removed, cur flipped if
 //                       something was removed.  Every kernel before it read the same head
 //
@@ -176,7 +250,8 @@ static_assert(sizeof(JgAwaitHead) == 16, "the table's head is one 16-byte record
 #define JG_AH_N (JG_AH_LEFT + 1u)                // the head as this pass leaves it
 #define JG_AH_CUR (JG_AH_N + 1u)
 #define JG_AH_GATE (JG_AH_CUR + 1u)              // the gate's verdict: the step's general-path rows as this pass saw them
-#define JG_AH_WORDS (JG_AH_GATE + 1u)
+#define JG_AH_MARKED (JG_AH_GATE + 1u)            // the waiters the step's cancel marked
+#define JG_AH_WORDS (JG_AH_MARKED + 1u)
 
 struct JgAwaitKeptArgs {
   uint32_t m;       // staged rows, appended first
@@ -197,6 +272,11 @@ struct JgAwaitKeptArgs {
   const uint64_t* total;  // [1] (k_scan_block_sums)
   uint4* out;             // [cap] rows of three 16-byte pieces (device)
   uint64_t* hdr;          // [JG_AH_WORDS]
+  const uint64_t* keys;   // [n_keys] the step's cancel: sorted, distinct, every one within mask (staged behind the rows)
+  uint64_t* mpart;        // [parts] the waiters each workgroup of the mark pass marked
+  uint64_t mask;
+  uint32_t n_keys;        // 0: the step carries no cancel
+  uint32_t pad;
 };
 
 __device__ __forceinline__ bool jg_await_gated(const uint32_t* gate) { return gate && *gate; }
@@ -212,6 +292,11 @@ __global__ __launch_bounds__(JG_BLOCK) void k_await_append(JgAwaitKeptArgs a) {
   if ((uint64_t)n + a.m > a.room) return;                // (never taken: refused by the host's bound)
   const size_t i = (size_t)blockIdx.x * JG_BLOCK + threadIdx.x;
   if (i < (size_t)a.m * 3) a.buf[cur][(size_t)n * 3 + i] = a.rows[i];
+}
+
+__global__ __launch_bounds__(JG_BLOCK) void k_await_mark_kept(JgAwaitKeptArgs a) {
+  if (jg_await_gated(a.gate)) return;
+  jg_await_mark_tiles(a.buf[a.head->cur & 1u], jg_await_n_eff(a, a.head->n), a.tiles, a.parts, a.keys, a.n_keys, a.mask, a.mpart);
 }
 
 __global__ __launch_bounds__(JG_BLOCK) void k_await_count_kept(JgDev d, JgAwaitKeptArgs a) {
@@ -234,7 +319,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_await_count_kept(JgDev d, JgAwaitK
     const uint64_t commit = jg_read_commit(d, g, f);
     asm volatile("" ::"v"(f), "v"(term_now), "v"(head), "v"(pw), "v"(col), "v"(run_hi));  // (as in k_await_count: one round trip)
     const uint32_t role = f & JGF_ROLE_MASK, fault = (f & JGF_FAULT_MASK) >> JGF_FAULT_SHIFT;
-    const uint32_t v = in ? jg_await_verdict(role, fault, term_now, commit, jg_awt_u64(w1.x, w1.y), jg_awt_u64(w1.z, w1.w),
+    const uint32_t v = in ? jg_await_verdict(w0.y, role, fault, term_now, commit, jg_awt_u64(w1.x, w1.y), jg_awt_u64(w1.z, w1.w),
                                              jg_awt_u64(w2.x, w2.y), a.now)
                           : 0u;
     if (in) a.verdict[i] = (uint8_t)v;
@@ -297,6 +382,8 @@ __global__ __launch_bounds__(JG_BLOCK) void k_await_header(JgAwaitKeptArgs a) {
   }
   if (a.stats) jg_parts_reduce<JG_AWT_WORDS>(a.part, a.parts, a.hdr + JG_AH_STATS, JgNeverMax());
   else if (threadIdx.x < JG_AWT_WORDS) a.hdr[JG_AH_STATS + threadIdx.x] = 0;
+  if (a.n_keys) jg_parts_reduce<1>(a.mpart, a.parts, a.hdr + JG_AH_MARKED, JgNeverMax());
+  else if (threadIdx.x == 0) a.hdr[JG_AH_MARKED] = 0;
   if (threadIdx.x) return;
   const uint32_t n = jg_await_n_eff(a, a.head->n), cur = a.head->cur & 1u;
   const uint64_t total = *a.total, given = total < a.cap ? total : a.cap;

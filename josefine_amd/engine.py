@@ -436,8 +436,9 @@ class BatchedRaft(_Hosting):
         keyword arguments of `poll` as a dict - the poll travels with the step, sees the engine exactly as the step leaves
         it and is handed out by `node_poll` once the step's outbox has been viewed.  completions (jg_step_node_awaited,
         ABI v23; with keep): dict(groups=, block_ids=, tokens=, terms=0, deadlines_ms=0, now_ms=, limit=None, peek=False,
-        stats=False) - the waiters of `await_blocks` (optional: without them the step only watches) are registered and the
-        watch of `watch_completions` is made behind the step; `node_completions` hands out the answer."""
+        stats=False, cancel_keys=(), cancel_mask=2**64 - 1) - the waiters of `await_blocks` (optional: without them the
+        step only watches) are registered, the cancel of `cancel_waiters` (ABI v24; optional) is made and the watch of
+        `watch_completions` is made behind the step; `node_completions` hands out the answer."""
         self._flush_pending()
         flags = (capi.NODE_LEADER_HALF if leader else 0) | (capi.NODE_FOLLOWER_HALF if follower else 0) | \
                 (capi.NODE_TICK if tick else 0) | (capi.NODE_ASYNC if async_ else 0) | \
@@ -449,7 +450,7 @@ class BatchedRaft(_Hosting):
             p = held = None
             if poll is not None:
                 p, held, parts = self._poll_request(**poll)
-            req, rows, want_stats = self._await_request(**completions)  # (`rows`: what req points at, alive over the call)
+            req, rows, want_stats = self._await_request(**completions)  # (`rows`, req.held: what req points at, alive over the call)
             self._check(self.api.step_node_awaited(self._h, int(now_ms), flags, C.byref(p) if p is not None else None, C.byref(req)))
             del held
             self._await_n = getattr(self, "_await_n", 0) + len(rows)  # (the bound: what the views take off it is not known yet)
@@ -468,7 +469,7 @@ class BatchedRaft(_Hosting):
                 None if completions is None else (want_stats, not completions.get("peek", False)))
 
     def _await_request(self, groups=(), block_ids=(), tokens=(), terms=0, deadlines_ms=0, now_ms: int = 0, limit: Optional[int] = None,
-                       peek: bool = False, stats: bool = False):
+                       peek: bool = False, stats: bool = False, cancel_keys=(), cancel_mask: int = 2**64 - 1):
         """jg_node_await_request from the keyword arguments of `await_blocks` and `watch_completions`"""
         groups = np.atleast_1d(np.asarray(groups))
         rows = np.zeros(len(groups), capi.AWAIT_ROW_DTYPE)
@@ -482,13 +483,18 @@ class BatchedRaft(_Hosting):
         req.rows, req.n = rows.ctypes.data if len(rows) else None, len(rows)
         req.flags, req.want_stats, req.now_ms = capi.WATCH_PEEK if peek else 0, 1 if stats else 0, int(now_ms)
         req.cap = have if limit is None else max(0, min(int(limit), have))
+        keys = np.ascontiguousarray(np.atleast_1d(np.asarray(cancel_keys, dtype=np.uint64)))
+        if len(keys):
+            req.cancel_keys, req.cancel_n, req.cancel_mask = keys.ctypes.data, len(keys), int(cancel_mask)
+            req.held = keys
         return req, rows, bool(stats)
 
     def node_completions(self):
         """jg_node_await_view: the answer of the completion request that travelled with the kept step whose outbox
         `node_outbox` viewed last, as host copies: {"answer": what `watch_completions` returns for the same arguments -
-        (rows, total) or (rows, total, stats) - and "redone": the step had general-path rows and the chain ran behind its
-        catch-up pass (informational)}.  A step that carried no request: {"redone": False}."""
+        (rows, total) or (rows, total, stats) - "marked": the waiters the step's cancel newly marked (what `cancel_waiters`
+        returns), and "redone": the step had general-path rows and the chain ran behind its catch-up pass
+        (informational)}.  A step that carried no request: {"redone": False}."""
         if not hasattr(self.api, "node_await_view"):
             raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}node_await_view")
         v = capi.NodeAwait()
@@ -503,7 +509,7 @@ class BatchedRaft(_Hosting):
         out = (rows, int(v.total))
         if self.__dict__.get("_viewed_await_stats", False):
             out += ({name: int(getattr(v.stats, name)) for name, _ in capi.AwaitStats._fields_},)
-        return {"answer": out, "redone": bool(v.state & capi.NODE_POLL_REDONE)}
+        return {"answer": out, "marked": int(v.marked), "redone": bool(v.state & capi.NODE_POLL_REDONE)}
 
     def _view_await(self):
         """behind a view of a kept step's outbox: the waiters its completion request removed leave the count that
@@ -943,6 +949,18 @@ class BatchedRaft(_Hosting):
         self._check(fn(self._h, rows.ctypes.data, len(rows)))
         self._await_n = getattr(self, "_await_n", 0) + len(rows)
         return len(rows)
+
+    def cancel_waiters(self, keys, mask: int = 2**64 - 1) -> int:
+        """jg_engine_await_cancel (ABI v24): withdraw every outstanding waiter whose `token & mask` is among `keys` (any
+        order, repeats allowed; at most capi.AWAIT_CANCEL_MAX) - exact tokens with the default mask, connections with
+        mask=0xFFFFFFFF00000000 and `conn << 32` as keys, everything with keys=[0], mask=0.  The waiters are marked, not
+        removed: the next `watch_completions` delivers them with state capi.DONE_CANCELLED, in registration order.  Returns
+        the number newly marked."""
+        fn = self._await_api("engine_await_cancel")
+        keys = np.ascontiguousarray(np.atleast_1d(np.asarray(keys, dtype=np.uint64)))
+        marked = C.c_size_t(0)
+        self._check(fn(self._h, keys.ctypes.data if len(keys) else None, len(keys), int(mask), C.byref(marked)))
+        return int(marked.value)
 
     def watch_completions(self, now_ms: int = 0, limit: Optional[int] = None, peek: bool = False, stats: bool = False):
         """jg_engine_watch_completions: the waiters that are done at `now_ms` - applied, lost or expired, the verdict in

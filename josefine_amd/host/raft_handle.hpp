@@ -408,6 +408,15 @@ class BatchedRaft {
     if (total) *total = tot;
     return out;
   }
+  // Withdrawing waiters (jg_engine_await_cancel, ABI v24; only callers need a library that has it): every outstanding waiter
+  // whose token & mask is among `keys` (any order, repeats allowed) is marked and leaves at the next watch_completions with
+  // state JG_DONE_CANCELLED, in registration order - exact tokens with the default mask, connections with the connection id
+  // in the token's high bits and a mask over them, everything with keys {0} and mask 0.  Returns the waiters newly marked.
+  size_t cancel_waiters(const std::vector<uint64_t>& keys, uint64_t mask = UINT64_MAX) {
+    size_t marked = 0;
+    check(jg_engine_await_cancel(e_, keys.data(), keys.size(), mask, &marked));
+    return marked;
+  }
   // One poll per tick (jg_engine_poll, ABI v18; only callers need a library that has it): the parts `want` names of
   // watch_leaders, watch_replicas, watch_commits, census and replication_census over [g0, g0 + n) in ONE call - one settle,
   // one device pass over the slots, one synchronisation - each exactly as its own call answers it, the shadows shared with
@@ -501,18 +510,22 @@ class BatchedRaft {
   // Completions behind a kept node step (jg_step_node_awaited / jg_node_await_view, ABI v23; only callers need a library
   // that has them): the step registers `a.rows` and then watches, behind its own kernels (and behind the poll `q`, if not
   // null); node_completions() hands the answer out once step_node_finish has served that step.  The answer is what
-  // await_blocks(a.rows) and watch_completions(a.now_ms, a.limit, a.peek) would have returned between that step and the
-  // next.  The table's room is checked against a bound: what outstanding steps' watches remove counts once they are finished.
+  // await_blocks(a.rows), cancel_waiters(a.cancel_keys, a.cancel_mask) (ABI v24; no keys: no cancel) and
+  // watch_completions(a.now_ms, a.limit, a.peek) would have returned between that step and the next.  The table's room is
+  // checked against a bound: what outstanding steps' watches remove counts once they are finished.
   struct AwaitRequest {
     std::vector<jg_await_row> rows;
     uint64_t now_ms = 0;
     size_t limit = SIZE_MAX;
     bool peek = false, stats = false;
+    std::vector<uint64_t> cancel_keys;  // withdrawn between the registration and the watch (the step's own rows too)
+    uint64_t cancel_mask = UINT64_MAX;
   };
   struct Completions {
     std::vector<jg_done_row> rows;
     size_t total = 0;
     jg_await_stats stats{};  // zero unless wanted
+    size_t marked = 0;       // the waiters the step's cancel newly marked
   };
   void step_node_awaited(uint64_t now_ms, uint32_t flags, const PollRequest* q, const AwaitRequest& a) {
     flush_rows();
@@ -522,6 +535,7 @@ class BatchedRaft {
     w.rows = a.rows.data(), w.n = a.rows.size();
     w.flags = a.peek ? (uint32_t)JG_WATCH_PEEK : 0u, w.want_stats = a.stats ? 1u : 0u;
     w.now_ms = a.now_ms, w.cap = a.limit;
+    if (!a.cancel_keys.empty()) w.cancel_keys = a.cancel_keys.data(), w.cancel_n = a.cancel_keys.size(), w.cancel_mask = a.cancel_mask;
     check(jg_step_node_awaited(e_, now_ms, flags | (uint32_t)JG_NODE_ASYNC | (uint32_t)JG_NODE_KEEP, q ? &p : nullptr, &w));
     step_blocks_.emplace_back();
     step_blocks_.back().swap(pending_blocks_);  // (as step_node_begin)
@@ -532,7 +546,7 @@ class BatchedRaft {
     check(jg_node_await_view(e_, &v));
     Completions c;
     if (v.rows_n) c.rows.assign(v.rows, v.rows + v.rows_n);
-    c.total = v.total, c.stats = v.stats;
+    c.total = v.total, c.stats = v.stats, c.marked = v.marked;
     if (attached) *attached = v.attached != 0;
     if (redone) *redone = (v.state & JG_NODE_POLL_REDONE) != 0;
     return c;
@@ -1096,6 +1110,10 @@ class BatchedEventLoop {
       typename Raft::AwaitRequest a;
       if (source) a.rows = source(at);
       a.now_ms = at, a.limit = limit;
+      if (!cancels_.empty()) {  // cancel_tokens: the oldest key set travels with this step
+        a.cancel_keys.swap(cancels_.front().first), a.cancel_mask = cancels_.front().second;
+        cancels_.pop_front();
+      }
       BatchedRaft::PollRequest qq;
       if (poll_q_) {
         qq = *poll_q_;
@@ -1108,6 +1126,21 @@ class BatchedEventLoop {
       const typename Raft::Completions c = r->node_completions(&attached, &redone);
       if (attached && sink) sink(c.rows, redone);
     };
+  }
+
+  // Withdraw waiters from inside the loop (ABI v24; with set_completions): the keys are attached to the next awaited tick's
+  // step - registered, cancelled, watched, in that order - and the withdrawn waiters reach the sink as JG_DONE_CANCELLED rows.
+  // Calls with the same mask before that tick are merged into one key set (while it stays within JG_AWAIT_CANCEL_MAX); a
+  // different mask starts a key set of its own, for the tick after.  Only awaited ticks carry a cancel: without
+  // set_completions the call throws, and on a loop whose in_flight is below 2 - no tick is awaited there - the keys wait
+  // until it is raised; such a loop cancels with BatchedRaft::cancel_waiters between its ticks.
+  void cancel_tokens(const std::vector<uint64_t>& keys, uint64_t mask = UINT64_MAX) {
+    if (!begin_awaited_) throw EngineError(JG_EINVAL, "cancel_tokens: no awaited ticks (set_completions first)");
+    if (keys.empty()) return;
+    if (!cancels_.empty() && cancels_.back().second == mask && cancels_.back().first.size() + keys.size() <= JG_AWAIT_CANCEL_MAX)
+      cancels_.back().first.insert(cancels_.back().first.end(), keys.begin(), keys.end());
+    else
+      cancels_.emplace_back(keys, mask);
   }
 
   explicit BatchedEventLoop(BatchedRaft& raft, uint32_t n_groups) : raft_(raft), G_(n_groups), answers_to_(n_groups, 0) {
@@ -1311,6 +1344,7 @@ class BatchedEventLoop {
   std::shared_ptr<BatchedRaft::PollRequest> poll_q_;       // set_poll's request: an awaited step carries it along
   std::function<void(uint64_t, uint32_t)> begin_awaited_;  // set_completions: the step with the request(s) attached ...
   std::function<void()> view_awaited_;                     // ... and its done rows to the sink
+  std::deque<std::pair<std::vector<uint64_t>, uint64_t>> cancels_;  // cancel_tokens: (keys, mask) per awaited tick to come
   std::deque<bool> awaited_steps_;                         // per open step: was it begun with the completion request
   std::deque<Message> local_;
   std::map<uint64_t, Response> requests_;

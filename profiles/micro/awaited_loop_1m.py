@@ -4,6 +4,8 @@ block is committed already; the table stays at 1 M, the others wait).  One mode 
 
   plain    no attachment: jg_step_node, the older step's outbox viewed, its rows drained by view
   awaited  jg_step_node_awaited on every step: the tick's waiters registered and the watch made behind the step
+  cancelled  awaited, and a cancel of 16 exact tokens travels with every step (ABI v24): 16 of the waiters that wait are
+           withdrawn and leave with the tick's watch, beside the 1 %
   sync     what a loop could do before ABI v23: the outstanding step viewed first (the three calls are refused while a
            kept step is outstanding), then jg_engine_await_blocks + jg_engine_watch_completions - one tick in flight
 
@@ -66,8 +68,11 @@ def main(mode, slots=1 << 20, ticks=80, warmup=16):
         r = rows(t)
         t0 = time.perf_counter()
         now = 100 * (t + 1)
-        if mode == "awaited":
+        if mode in ("awaited", "cancelled"):
             q = capi.NodeAwaitRequest(r.ctypes.data, len(r), 0, 0, now, len(out))
+            if mode == "cancelled":
+                keys = np.arange(16 * t, 16 * t + 16, dtype=np.uint64)  # (tokens of waiters that wait: registered at the start)
+                q.cancel_keys, q.cancel_n, q.cancel_mask = keys.ctypes.data, 16, 2**64 - 1
             ok(api.step_node_awaited(h, now, flags, None, C.byref(q)))
         else:
             ok(api.step_node(h, now, flags))
@@ -81,19 +86,20 @@ def main(mode, slots=1 << 20, ticks=80, warmup=16):
         elif open_steps == 2:
             finish()
             open_steps -= 1
-            if mode == "awaited":
+            if mode in ("awaited", "cancelled"):
                 ok(api.node_await_view(h, C.byref(view)))
-                assert view.attached
+                assert view.attached and view.marked == (16 if mode == "cancelled" else 0)
                 delivered += view.rows_n
         times.append(time.perf_counter() - t0)
     while open_steps:
         finish()
         open_steps -= 1
-        if mode == "awaited":
+        if mode in ("awaited", "cancelled"):
             ok(api.node_await_view(h, C.byref(view)))
             delivered += view.rows_n
     if mode != "plain":
-        assert delivered == (warmup + ticks) * per_tick, (delivered, (warmup + ticks) * per_tick)
+        want = (warmup + ticks) * (per_tick + (16 if mode == "cancelled" else 0))
+        assert delivered == want, (delivered, want)
     ms = np.array(times[warmup:]) * 1e3
     print(json.dumps(dict(mode=mode, slots=G, R=R, waiters=W, done_per_tick=per_tick if mode != "plain" else 0, ticks=ticks,
                           ms_per_tick_median=round(float(np.median(ms)), 3), q1=round(float(np.percentile(ms, 25)), 3),
