@@ -60,16 +60,16 @@ int await_append_shard(jg_engine* e, const jg_await_row* rows, size_t n) {
 
 // One watch's chain of kernels over ONE block of scratch (the rows' landing area; an awaited step's staged rows and header
 // block too): the table's own buffers, verdict bytes, tile counts and partial records serve both.  `kept`: the chain of an
-// awaited node step - the head is the device's, n is the host's bound on it.
+// awaited node step - the head is the device's, n is the host's bound on it.  A synchronous cancel is the same plan with
+// nothing to deliver and its keys in the block: the mark pass alone.
 struct AwaitPlan {
   bool kept = false;
   uint32_t n = 0, tiles = 0, parts = 0;  // the waiters the passes are launched for
   size_t m = 0, wcap = 0;                // staged rows (kept); rows the landing area holds
-  size_t ck = 0;                         // the cancel's keys (kept: staged behind the rows)
+  size_t ck = 0;                         // the cancel's keys (kept: staged behind the rows; synchronous: a cancel's plan alone)
   Carve c;
   size_t o_out = 0, o_rows = 0, o_hdr = 0, o_keys = 0;
   JgAwaitArgs a{};
-  JgAwaitKeptArgs k{};
 };
 
 void await_plan(AwaitPlan& P, bool kept, size_t n, size_t m, size_t cap, size_t ck = 0) {
@@ -78,31 +78,29 @@ void await_plan(AwaitPlan& P, bool kept, size_t n, size_t m, size_t cap, size_t 
   P.parts = std::min<uint32_t>(P.tiles, JG_AWT_PARTS);
   P.wcap = std::min<size_t>(cap, n);
   P.o_out = P.c.sect(P.wcap * sizeof(jg_done_row));
-  if (kept) P.o_rows = P.c.sect(m * sizeof(jg_await_row)), P.o_hdr = P.c.sect(JG_AH_WORDS * 8), P.o_keys = P.c.sect(ck * 8);
+  if (kept) P.o_rows = P.c.sect(m * sizeof(jg_await_row)), P.o_hdr = P.c.sect(JG_AH_WORDS * 8);
+  if (kept || ck) P.o_keys = P.c.sect(ck * 8);
 }
 
-// the arguments of every pass over block B; `gate`: null, or the device word that makes an awaited step's chain leave
-// everything alone (jg_await.h)
+// the arguments of every pass over block B, one record (JgAwaitArgs): what both chains read, then what each reads alone;
+// `gate`: null, or the device word that makes an awaited step's chain leave everything alone (jg_await.h)
 void await_bind(jg_engine* e, AwaitPlan& P, char* B, bool peek, bool stats, uint64_t now_ms, uint32_t add, const uint32_t* gate,
                 uint64_t cmask = 0) {
   jg_engine::AwaitTable& t = e->await;
-  if (!P.kept) {
-    JgAwaitArgs& a = P.a;
-    a.n = P.n, a.add = add, a.peek = peek ? 1u : 0u, a.tiles = P.tiles, a.parts = P.parts, a.now = now_ms, a.cap = P.wcap;
-    a.tab = t.buf[t.cur], a.dst = t.buf[t.cur ^ 1], a.verdict = t.verdict;
-    a.bsum = t.bsum, a.part = t.part;
-    a.sum = (uint64_t*)(t.misc + AWT_O_SUM), a.total = (const uint64_t*)(t.misc + AWT_O_TOTAL);
-    a.out = (uint4*)(B + P.o_out);
-    return;
+  JgAwaitArgs& a = P.a;
+  a.peek = peek ? 1u : 0u, a.tiles = P.tiles, a.parts = P.parts, a.n_keys = (uint32_t)P.ck;
+  a.now = now_ms, a.cap = P.wcap, a.mask = cmask;
+  a.buf[0] = t.buf[0], a.buf[1] = t.buf[1], a.verdict = t.verdict, a.bsum = t.bsum, a.part = t.part;
+  a.total = (const uint64_t*)(t.misc + AWT_O_TOTAL), a.out = (uint4*)(B + P.o_out);
+  a.keys = (const uint64_t*)(B + P.o_keys), a.mpart = t.mpart;
+  if (!P.kept) {  // the table's view is the host's
+    a.n = P.n, a.cur = (uint32_t)t.cur, a.add = add;
+    a.sum = (uint64_t*)(t.misc + AWT_O_SUM), a.marked = (uint64_t*)(t.misc + AWT_O_MARKED);
+  } else {  // ... the head's
+    a.m = (uint32_t)P.m, a.room = (uint32_t)t.cap, a.stats = stats ? 1u : 0u;
+    a.head = (JgAwaitHead*)(t.misc + AWT_O_HEAD), a.gate = gate;
+    a.rows = (const uint4*)(B + P.o_rows), a.hdr = (uint64_t*)(B + P.o_hdr);
   }
-  JgAwaitKeptArgs& k = P.k;
-  k.m = (uint32_t)P.m, k.room = (uint32_t)t.cap, k.peek = peek ? 1u : 0u, k.tiles = P.tiles, k.parts = P.parts, k.stats = stats ? 1u : 0u;
-  k.now = now_ms, k.cap = P.wcap;
-  k.head = (JgAwaitHead*)(t.misc + AWT_O_HEAD), k.gate = gate;
-  k.rows = (const uint4*)(B + P.o_rows), k.buf[0] = t.buf[0], k.buf[1] = t.buf[1], k.verdict = t.verdict;
-  k.bsum = t.bsum, k.part = t.part, k.total = (const uint64_t*)(t.misc + AWT_O_TOTAL);
-  k.out = (uint4*)(B + P.o_out), k.hdr = (uint64_t*)(B + P.o_hdr);
-  k.keys = (const uint64_t*)(B + P.o_keys), k.mpart = t.mpart, k.mask = cmask, k.n_keys = (uint32_t)P.ck;
 }
 
 // the whole chain on the engine's stream (`job`: where the device reads the scan job): [the append, the mark pass,] the
@@ -126,20 +124,20 @@ int await_queue(jg_engine* e, const AwaitPlan& P, const JgScanJob* job, bool sta
     }
   } else {
     if (P.m) {
-      hipLaunchKernelGGL(k_await_append, dim3((uint32_t)((P.m * 3 + JG_BLOCK - 1) / JG_BLOCK)), block, 0, e->stream, P.k);
+      hipLaunchKernelGGL(k_await_append, dim3((uint32_t)((P.m * 3 + JG_BLOCK - 1) / JG_BLOCK)), block, 0, e->stream, P.a);
       e->n_launch++;
     }
     if (P.ck) {  // (behind the append: the step's own rows can be withdrawn by it)
-      hipLaunchKernelGGL(k_await_mark_kept, dim3(P.parts), block, 0, e->stream, P.k);
+      hipLaunchKernelGGL(k_await_mark_kept, dim3(P.parts), block, 0, e->stream, P.a);
       e->n_launch++;
     }
-    hipLaunchKernelGGL(k_await_count_kept, dim3(P.parts), block, 0, e->stream, e->dev, P.k);
+    hipLaunchKernelGGL(k_await_count_kept, dim3(P.parts), block, 0, e->stream, e->dev, P.a);
     hipLaunchKernelGGL(k_scan_block_sums, dim3(1), block, 0, e->stream, job, total);
     if (P.wcap) {
-      hipLaunchKernelGGL(k_await_write_kept, dim3(P.tiles), block, 0, e->stream, e->dev, P.k);
+      hipLaunchKernelGGL(k_await_write_kept, dim3(P.tiles), block, 0, e->stream, e->dev, P.a);
       e->n_launch++;
     }
-    hipLaunchKernelGGL(k_await_header, dim3(1), block, 0, e->stream, P.k);
+    hipLaunchKernelGGL(k_await_header, dim3(1), block, 0, e->stream, P.a);
     e->n_launch += 3;
   }
   HIPCHK(hipGetLastError());
@@ -178,29 +176,26 @@ int await_shard(jg_engine* e, uint32_t flags, uint64_t now_ms, uint32_t add, jg_
   return JG_OK;
 }
 
-// one single-device engine's part of a cancel: the mark pass over its table and the reduce, the keys (sorted, distinct,
-// within mask: await_keys_check) staged into the engine's staging; *marked the waiters newly marked.  The caller has settled
-// the engine's JG_NODE_ASYNC step
+// one single-device engine's part of a cancel: the mark pass over its table and the reduce, planned and bound as a watch
+// is, the keys (sorted, distinct, within mask: await_keys_check) staged into the engine's staging; *marked the waiters
+// newly marked.  The caller has settled the engine's JG_NODE_ASYNC step
 int await_cancel_shard(jg_engine* e, const std::vector<uint64_t>& keys, uint64_t mask, size_t* marked) {
   *marked = 0;
   HIPCHK(hipSetDevice(e->device));
   jg_engine::AwaitTable& t = e->await;
   if (!t.n) return JG_OK;
-  Carve c;
-  c.sect(keys.size() * 8);
+  AwaitPlan P;
+  await_plan(P, false, t.n, 0, 0, keys.size());
   char* B = nullptr;
-  if (const int rc = c.on_staging(e, B)) return rc;
-  JgAwaitMarkArgs a{};
-  a.n = (uint32_t)t.n, a.tiles = (a.n + JG_AWT_TILE - 1) / JG_AWT_TILE, a.parts = std::min<uint32_t>(a.tiles, JG_AWT_PARTS);
-  a.n_keys = (uint32_t)keys.size(), a.mask = mask;
-  a.tab = t.buf[t.cur], a.keys = (const uint64_t*)B, a.part = t.mpart, a.sum = (uint64_t*)(t.misc + AWT_O_MARKED);
-  HIPCHK(hipMemcpyAsync(B, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(k_await_mark, dim3(a.parts), dim3(JG_BLOCK), 0, e->stream, a);
-  hipLaunchKernelGGL(k_await_mark_sum, dim3(1), dim3(JG_BLOCK), 0, e->stream, a);
+  if (const int rc = P.c.on_staging(e, B)) return rc;
+  await_bind(e, P, B, false, false, 0, 0, nullptr, mask);
+  HIPCHK(hipMemcpyAsync(B + P.o_keys, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_await_mark, dim3(P.parts), dim3(JG_BLOCK), 0, e->stream, P.a);
+  hipLaunchKernelGGL(k_await_mark_sum, dim3(1), dim3(JG_BLOCK), 0, e->stream, P.a);
   e->n_launch += 2;
   HIPCHK(hipGetLastError());
   uint64_t got = 0;
-  HIPCHK(hipMemcpyAsync(&got, a.sum, 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(&got, P.a.marked, 8, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   *marked = (size_t)got;
   return JG_OK;
@@ -288,7 +283,7 @@ int node_await_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate) {
   if (const int rc = await_queue(e, P, (const JgScanJob*)(o.h_await + NODE_AWAIT_JOB), aw.stats)) return rc;
   HIPCHK(hipEventRecord(o.ev_kernels, e->stream));
   HIPCHK(hipStreamWaitEvent(nd.down, o.ev_kernels, 0));
-  HIPCHK(hipMemcpyAsync(o.h_await + NODE_AWAIT_HDR, P.k.hdr, JG_AH_WORDS * 8, hipMemcpyDeviceToHost, nd.down));
+  HIPCHK(hipMemcpyAsync(o.h_await + NODE_AWAIT_HDR, P.a.hdr, JG_AH_WORDS * 8, hipMemcpyDeviceToHost, nd.down));
   if (!aw.redone) {  // (the pass behind the catch-up pass lands where the first one did: its copy may still be in flight)
     const size_t last = nd.await_guess_known ? nd.await_guess : P.wcap;  // (no awaited step finished yet: min(cap, bound))
     aw.copied = std::min(P.wcap, last + last / 32 + 4096);               // (the margin of the fsm rows: node_keep_tail)
@@ -296,7 +291,7 @@ int node_await_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate) {
   if (const size_t bytes = aw.copied * sizeof(jg_done_row)) {
     o.l_await.n = 0;
     HIPCHK(o.l_await.reserve(bytes));
-    HIPCHK(hipMemcpyAsync(o.l_await.p, P.k.out, bytes, hipMemcpyDeviceToHost, nd.down));
+    HIPCHK(hipMemcpyAsync(o.l_await.p, P.a.out, bytes, hipMemcpyDeviceToHost, nd.down));
   }
   return JG_OK;
 }
