@@ -54,7 +54,6 @@ struct jg_dense_cluster {
     std::vector<uint32_t> n_in, in_off;
     std::vector<JgXqRec*> xq_keep;  // per node, lazily: where the exceptional rows that stay are compacted
     uint32_t* bk_hist = nullptr;  // bucket counts / offsets, scatter cursors, scan-tile bases (k_route_hist ... _sort_build)
-    uint32_t bk_cap = 0;
     // job tables of the round's multi launches (one launch for all nodes / senders / steps): a pinned staging
     // the host fills and its device copy, in slices of JOB_SLICE bytes
     static constexpr size_t JOB_SLICE = 16384;

@@ -432,10 +432,7 @@ __global__ __launch_bounds__(JG_BLOCK) void k_votes_validate(JgVoteMail m, uint3
 // wordmail bit of its partition (the census's first copy, the receiving half's answer), so the union of the addressees'
 // wordmail words says which partitions' control words are dirty (R x G / 8 bytes read instead of 8 x R x G bytes written
 // per round: 0.6 MB against 40 MB at 1 M x 5); then the bitmaps themselves (the thread that brought a word clears it: the
-// lanes work from the copy in LDS).
-// (`a`, `b`: two more word ranges that go back to zero with the round's mail - the transport's tallies and its bucket
-// counters, k_route_clear's job: one launch less per round; `cp_*`: the round's job tables on their way from the host's pinned
-// staging to the device, k_copy_words' job: another one)
+// lanes work from the copy in LDS).  Run by k_apply_rows_clear_multi's last row of workgroups.
 __device__ __forceinline__ void jg_votes_clear_mail(const JgVoteMail& m) {
   __shared__ JgBitChunk s;
   const uint32_t n_chunks = (m.words + JG_VOTE_CHUNK - 1) / JG_VOTE_CHUNK;
@@ -454,15 +451,17 @@ __device__ __forceinline__ void jg_votes_clear_mail(const JgVoteMail& m) {
     }
   }
 }
-// (m.words = 0: no mail to clear - the round's mail was cleared beside the injected rows' step of the round before, k_apply_rows_clear_multi)
-__global__ __launch_bounds__(JG_BLOCK) void k_votes_clear(JgVoteMail m, uint32_t* __restrict__ a, uint32_t na, uint32_t* __restrict__ b, uint32_t nb,
-                                                          uint64_t* __restrict__ cp_dst = nullptr, const uint64_t* __restrict__ cp_src = nullptr, uint32_t cp_n = 0) {
+// The head of a routed round with the vote mail: the round's job tables on their way from the host's pinned staging to the
+// device (`cp_*`: k_copy_words' job) and two word ranges that go back to zero (`a`, `b`: the transport's tallies and its bucket
+// counters, k_route_clear's job) - one launch instead of three.  It clears no mail, whatever its name says (kept: the recorded
+// profiles name it): the round's mail was cleared beside the injected rows' step of the round before, k_apply_rows_clear_multi.
+__global__ __launch_bounds__(JG_BLOCK) void k_votes_clear(uint32_t* __restrict__ a, uint32_t na, uint32_t* __restrict__ b, uint32_t nb,
+                                                          uint64_t* __restrict__ cp_dst, const uint64_t* __restrict__ cp_src, uint32_t cp_n) {
   for (uint32_t i = blockIdx.x * JG_BLOCK + threadIdx.x; i < cp_n; i += gridDim.x * JG_BLOCK) cp_dst[i] = cp_src[i];
   for (uint32_t i = blockIdx.x * JG_BLOCK + threadIdx.x; i < na + nb; i += gridDim.x * JG_BLOCK) {
     if (i < na) a[i] = 0;
     else b[i - na] = 0;
   }
-  jg_votes_clear_mail(m);
 }
 // The injected rows' step of a routed round (blockIdx.y < n_jobs: a node's batch each, jg_apply_rows_body) and, beside it, the
 // clearing of the mail the round's receiving half has just read - the NEXT round's to fill (the last value of blockIdx.y): the

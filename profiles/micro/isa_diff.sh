@@ -31,8 +31,15 @@ def kernels(path):
             out[cur].append(ins)
     return out
 a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+import functools
+@functools.lru_cache(None)
 def dem(n):
     return subprocess.run(['c++filt', n], capture_output=True, text=True).stdout.strip().replace('(anonymous namespace)::', '').split('(')[0]
+# (a kernel whose parameter list changed has another symbol: one gone and one new under the same name are the same kernel)
+gone, new = {dem(k): k for k in a if k not in b}, {dem(k): k for k in b if k not in a}
+for name in set(gone) & set(new):
+    if sum(dem(k) == name for k in a) == 1 and sum(dem(k) == name for k in b) == 1:
+        a[new[name]] = a.pop(gone[name])
 same = [k for k in a if k in b and a[k] == b[k]]
 diff = [k for k in a if k in b and a[k] != b[k]]
 print(f"{len(same)} kernels / functions identical, {len(diff)} differ, {len([k for k in b if k not in a])} new, {len([k for k in a if k not in b])} gone")

@@ -840,7 +840,7 @@ class VoteMail:
         self.rowmail, self.wordmail = np.zeros((R, self.words), np.uint64), np.zeros((R, self.words), np.uint64)
         self.c = _JgVoteMail(R, G, self.words, 0, self._rec.ctypes.data, self.rowmail.ctypes.data, self.wordmail.ctypes.data)
 
-    def clear(self):  # (k_votes_clear: the control words and the bitmaps; the term / head columns keep their garbage)
+    def clear(self):  # (jg_votes_clear_mail: the control words and the bitmaps; the term / head columns keep their garbage)
         self.q_ctl[:], self.a_ctl[:], self.rowmail[:], self.wordmail[:] = 0, 0, 0, 0
 
     @staticmethod

@@ -504,7 +504,7 @@ VIS size_t hw_take_xq(Host* h, JgXqRec* out, size_t cap) {
 }
 VIS void hw_votes_clear(const JgVoteMail* m) {
   const JgVoteMail a = *m;
-  wg::launch(dim3(3), JG_BLOCK, [&] { k_votes_clear(a, nullptr, 0, nullptr, 0); });
+  wg::launch(dim3(3), JG_BLOCK, [&] { jg_votes_clear_mail(a); });  // (k_apply_rows_clear_multi's last row of workgroups)
 }
 '''
 

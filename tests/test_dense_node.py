@@ -600,30 +600,48 @@ def test_routed_transport_repeats_with_wide_keys():
 
 @pytest.mark.gpu
 def test_routed_round_argument_checks():
-    """Misuse is refused with JG_EINVAL, not executed: injected rows that carry blocks, a node with a
-    drain in transfer."""
+    """Misuse is refused with JG_EINVAL, not executed: injected rows that carry blocks, injected rows with a column
+    missing, a node with a drain in transfer.  And a refused call consumes nothing (the round's check phase reads only):
+    a twin cluster that makes the valid calls alone ends in the same state on every node."""
     from josefine_amd import DenseCluster as LibCluster, EngineError
+
+    def cluster():
+        nodes = [BatchedRaft(G, R, seed=5 + r, self_slots=np.full(G, r, np.uint8), flags=capi.CFG_SEPARATE_COMMIT_KEY)
+                 for r in range(R)]
+        elect_all(nodes[0])
+        nodes[0].drain_messages(), nodes[0].drain_applies()
+        lib = LibCluster(nodes)
+        lib.set_appends(1)
+        return nodes, lib
+
     G, R = 64, 3
-    nodes = [BatchedRaft(G, R, seed=5 + r, self_slots=np.full(G, r, np.uint8), flags=capi.CFG_SEPARATE_COMMIT_KEY)
-             for r in range(R)]
-    elect_all(nodes[0])
-    nodes[0].drain_messages(), nodes[0].drain_applies()
-    lib = LibCluster(nodes)
-    lib.set_appends(1)
+    nodes, lib = cluster()
+    twin, twin_lib = cluster()
     lib.round_routed(100, None)
+    twin_lib.round_routed(100, None)
     rows = nodes[1].upload_rows(kind=np.array([capi.CMD_APPEND_ENTRIES], np.uint8), group=np.array([3], np.uint32),
                                 aux=np.array([1], np.uint64), blk_id=np.array([7], np.uint64), blk_next=np.array([6], np.uint64))
     with pytest.raises(EngineError, match="cannot carry blocks"):
         lib.round_routed(200, [None, rows, None])
     rows.free()
-    nodes[2].apply(0, Command.Tick())
-    nodes[2].drain_prefetch()
+    rows = nodes[1].upload_rows(kind=np.array([capi.CMD_TICK], np.uint8), group=np.array([3], np.uint32))
+    rows.batch.flag = None  # (the column stays allocated: rows.free() below)
+    with pytest.raises(EngineError, match="all seven device columns are required"):
+        lib.round_routed(200, [None, rows, None])
+    rows.free()
+    for n in (nodes[2], twin[2]):  # (the drain is the engine's own business: the twin has one too)
+        n.apply(0, Command.Tick())
+        n.drain_prefetch()
     with pytest.raises(EngineError, match="drain is in transfer"):
         lib.round_routed(300, None)
-    nodes[2].drain_flush()
+    nodes[2].drain_flush(), twin[2].drain_flush()
     lib.round_routed(300, None)  # and the cluster carries on
+    twin_lib.round_routed(300, None)
     assert (nodes[0].read("fault") == 0).all()
-    lib.close()
+    for n in range(R):
+        for col in ("term", "role", "head", "commit", "fault"):
+            assert (nodes[n].read(col) == twin[n].read(col)).all(), (n, col)
+    lib.close(), twin_lib.close()
 
 
 @pytest.mark.gpu

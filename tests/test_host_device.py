@@ -27,6 +27,13 @@ def test_routed_round_with_the_vote_mail_through_the_engines_host_code():
     assert "2 passed" in out, out[-500:]
 
 
+def test_a_refused_routed_round_consumes_nothing_on_the_emulated_device():
+    """the routed round's check phase through the engine's host code: three refusals between valid rounds, and a twin cluster
+    that makes the valid calls alone ends in the same state"""
+    out = _run(["tests/test_dense_node.py", "-m", "gpu", "-k", "test_routed_round_argument_checks"])
+    assert "1 passed" in out, out[-500:]
+
+
 def test_the_default_path_on_the_emulated_device():
     """the stand-in held to tests the real device passes: the sparse step under the fuzzed command streams (every role, the
     chain, elections), the dense tick against the sparse path, the T-tick kernel, device-resident rows - through the C ABI"""

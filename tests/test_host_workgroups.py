@@ -115,7 +115,7 @@ def test_the_transports_kernels_on_random_emissions(R, seed, words):
 
 
 class KernelMailCluster(RoutedCluster):
-    """the routed round under JG_ROUTE_VOTE_WORDS as round_routed_impl launches it, kernels on the host: k_votes_clear,
+    """the routed round under JG_ROUTE_VOTE_WORDS as round_routed_impl launches it, kernels on the host: jg_votes_clear_mail,
     k_vote_half_multi (every node in one launch), the rows' steps, the dense round, then the transport (hw_route)"""
 
     def __init__(self, G, R, **kw):
