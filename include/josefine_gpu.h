@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 24u /* v24: jg_engine_await_cancel, jg_node_await_request.cancel_keys / cancel_n / cancel_mask, jg_node_await.marked, JG_DONE_CANCELLED (withdrawing waiters: a closed connection leaves the purgatory); v23: jg_step_node_awaited / jg_node_await_view (completions behind a kept node step: the purgatory with two ticks in flight); v22: jg_engine_await_open / jg_engine_await_blocks / jg_engine_watch_completions (the completion feed: fsm::Driver's notifications on the device); v21: jg_step_node_polled / jg_node_poll_view (a poll behind a kept node step: the feeds with two ticks in flight); v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 25u /* v25: jg_step_node_looked / jg_node_lookup_view, JG_NODE_LOOKUP_MAX (point queries behind a kept node step: Metadata with two ticks in flight); v24: jg_engine_await_cancel, jg_node_await_request.cancel_keys / cancel_n / cancel_mask, jg_node_await.marked, JG_DONE_CANCELLED (withdrawing waiters: a closed connection leaves the purgatory); v23: jg_step_node_awaited / jg_node_await_view (completions behind a kept node step: the purgatory with two ticks in flight); v22: jg_engine_await_open / jg_engine_await_blocks / jg_engine_watch_completions (the completion feed: fsm::Driver's notifications on the device); v21: jg_step_node_polled / jg_node_poll_view (a poll behind a kept node step: the feeds with two ticks in flight); v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -1352,6 +1352,48 @@ typedef struct jg_node_await {
   size_t marked;                      /* the waiters the step's cancel newly marked (ABI v24)               */
 } jg_node_await;
 int jg_node_await_view(jg_engine* e, jg_node_await* out);
+
+/* ---- point queries behind a kept node step (ABI v25) ----------------------------------------------
+ * jg_engine_lookup_groups is refused while kept steps are outstanding, like every call that reads.  A
+ * LOOKED step carries a point query with it, as a polled step carries its poll and an awaited step its
+ * completion request: the state of exactly these partitions - leader, term, head, commit, the progress
+ * heads - without a bubble in a loop that always has a step outstanding.
+ *
+ * CONTRACT.  Let S be the engine after kept step t is settled and before anything else touches it.  The
+ * answer viewed for step t is what jg_engine_lookup_groups(e, lookup, rows, match) writes when called on
+ * S: every byte of every row and every progress head.  The call defines no value of its own.  It reads
+ * state columns only: it writes no shadow, clock, table or column of the state machine, and a kept step
+ * with or without a lookup leaves every other result unchanged - the step's outbox, its drains, its poll
+ * and its completions.  jg_engine_lookup_groups itself stays refused while kept steps are outstanding;
+ * once none is the two may be mixed freely.
+ *
+ * jg_step_node_looked with lookup == NULL is exactly jg_step_node_awaited(e, now_ms, flags, poll, await).
+ * Otherwise the polled step's rules hold (JG_NODE_ASYNC | JG_NODE_KEEP, no multi-device parent), and
+ * *lookup and its host list are copied at entry: the caller's memory is free when the call returns.
+ * Accepted: a range (groups == NULL: g0, n) or a host list (unsorted, repeats allowed), optionally
+ * JG_LOOKUP_PROGRESS.  Refused with JG_EINVAL: JG_GROUPS_DEVICE (a device list's bounds are known only
+ * on the device, and a refusal that arrives a tick late is not worth having), n > JG_NODE_LOOKUP_MAX, an
+ * index >= G, a range out of bounds, a non-null self_slots, an unknown flag.  Every argument - `poll`
+ * and `await` by their own rules - is checked before anything of the step is queued: a refused call
+ * steps nothing and leaves the submitted rows queued.  n == 0 is an attached lookup with no rows.  The
+ * poll and the completion request, if attached, are queued first.
+ *
+ * jg_node_lookup_view answers for the kept step whose outbox jg_node_outbox_view finished last; JG_EINVAL
+ * if no kept step has been viewed yet.  attached == 0: that step carried no lookup (JG_OK, everything
+ * else 0).  The rows and the progress heads live in the set's pinned landing area (sized at entry: n is
+ * known, nothing is fetched later) and stay valid as long as that view's outbox columns do.  state:
+ * JG_NODE_POLL_REDONE as for the poll - the step had general-path rows, the pass behind its first pass
+ * wrote no row (the device saw the count) and ran once more behind the catch-up pass. */
+#define JG_NODE_LOOKUP_MAX 65536u     /* entries a step can carry: one staging piece of jg_engine_lookup_groups */
+int jg_step_node_looked(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_poll* poll /* may be NULL */,
+                        const jg_node_await_request* await /* may be NULL */, const jg_group_set* lookup /* may be NULL */);
+typedef struct jg_node_lookup {
+  uint32_t attached, state;           /* 1: the step carried a lookup; JG_NODE_POLL_REDONE                  */
+  const jg_group_state* rows;         /* [n], in the order asked                                            */
+  size_t n;
+  const uint64_t* match;              /* [n][R] progress heads, or NULL (JG_LOOKUP_PROGRESS not asked)      */
+} jg_node_lookup;
+int jg_node_lookup_view(jg_engine* e, jg_node_lookup* out);
 
 /* ---- a closed loop of dense node ticks ------------------------------------------------------------
  * All R nodes of every partition in ONE process (one engine per node, e.g. the three brokers of

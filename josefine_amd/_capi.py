@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -302,6 +302,14 @@ class NodeAwait(C.Structure):
                 ("stats", AwaitStats), ("marked", C.c_size_t)]
 
 
+NODE_LOOKUP_MAX = 65536  # jg_step_node_looked: the most entries a step can carry
+
+
+class NodeLookup(C.Structure):
+    """jg_node_lookup."""
+    _fields_ = [("attached", C.c_uint32), ("state", C.c_uint32), ("rows", C.c_void_p), ("n", C.c_size_t), ("match", C.c_void_p)]
+
+
 # mailbox words (josefine_gpu.h: JG_ANSWER / JG_AE)
 MAILBOX_NONE = (1 << 56) - 1
 
@@ -452,6 +460,8 @@ class Api:
         "node_poll_view": (C.c_int, [_P, C.POINTER(NodePoll)]),
         "step_node_awaited": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.POINTER(Poll), C.POINTER(NodeAwaitRequest)]),
         "node_await_view": (C.c_int, [_P, C.POINTER(NodeAwait)]),
+        "step_node_looked": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.POINTER(Poll), C.POINTER(NodeAwaitRequest), C.POINTER(GroupSet)]),
+        "node_lookup_view": (C.c_int, [_P, C.POINTER(NodeLookup)]),
     }
     # only the oracle has these
     _ORACLE_PROTOS = {
@@ -505,4 +515,5 @@ HEADER_SYMBOLS = [
     "jg_engine_await_open", "jg_engine_await_blocks", "jg_engine_watch_completions",
     "jg_step_node_awaited", "jg_node_await_view",
     "jg_engine_await_cancel",
+    "jg_step_node_looked", "jg_node_lookup_view",
 ]

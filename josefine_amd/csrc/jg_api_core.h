@@ -455,6 +455,15 @@ struct jg_engine {
     size_t copied = 0;                 // done rows the step's own copy brought home
     bool redone = false;               // queued once more, ungated, behind the catch-up pass (JG_NODE_POLL_REDONE)
   };
+  // the point query of a kept node step: what the set keeps of jg_group_set, and the step's own bookkeeping
+  struct NodeLookup {
+    bool on = false;                   // the step carries a lookup
+    uint32_t g0 = 0, n = 0;            // the range (listed == false), the entries
+    bool progress = false;             // JG_LOOKUP_PROGRESS
+    bool listed = false;               // a host list, staged in NodeOut::l_lookup_up
+    char* scratch = nullptr;           // the set's arena: the list, the rows, the progress heads, the header words
+    bool redone = false;               // queued once more, ungated, behind the catch-up pass (JG_NODE_POLL_REDONE)
+  };
   struct NodeOut {
     jg_leader_beat* h_beat = nullptr;  // pinned mirrors of the outbox columns
     uint64_t *h_ae = nullptr, *h_answer = nullptr, *h_hbc = nullptr, *h_aec = nullptr;
@@ -498,6 +507,11 @@ struct jg_engine {
     PinnedQueue<char> l_await_up;      // pinned: the step's staged rows, then its cancel keys, on their way up (bytes)
     PinnedQueue<char> l_await;         // pinned: where the done rows land (bytes); the first aw.copied rows came with the step
     jg_node_await await_view{};        // what jg_node_await_view hands out once the step's outbox has been viewed
+    // -- jg_step_node_looked: the point query that travels with the step (jg_api_lookup.h) ---------------------------------
+    NodeLookup lk;                     // the set as copied at entry (on == false: the step carries none)
+    PinnedQueue<char> l_lookup_up;     // pinned: the step's staged list on its way up (bytes)
+    PinnedQueue<char> l_lookup;        // pinned: where the rows, the progress heads and the header words land (bytes); sized at entry
+    jg_node_lookup lookup_view{};      // what jg_node_lookup_view hands out once the step's outbox has been viewed
   };
   struct NodeStep {
     // The two sets.  `newest` is the one the newest step took (a kept step takes the other one, a plain step the same one

@@ -112,6 +112,11 @@ int node_poll_finish(jg_engine* e, jg_engine::NodeOut& o);
 int node_await_stage(jg_engine::NodeOut& o, const jg_await_row* rows, const uint64_t* keys);
 int node_await_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate);
 int node_await_finish(jg_engine* e, jg_engine::NodeOut& o);
+// (jg_api_lookup.h) the point query that travels with a kept step: its list staged at entry, one launch queued behind the
+// step's kernels (its poll's and its completion request's), collected when its outbox is viewed
+int node_lookup_stage(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* list);
+int node_lookup_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate);
+int node_lookup_finish(jg_engine* e, jg_engine::NodeOut& o);
 
 // node_step (or node_settle's catch-up pass) is running: its halves' own node_settle calls are not another caller's
 struct InStep {
@@ -422,9 +427,10 @@ int node_publish(jg_engine* e, const NodeRun& s, uint32_t seq0, NodeClaim& claim
 
 // `poll`: the request of a polled step (jg_step_node_polled: checked, and a kept step's), or null; `await`: the completion
 // request of an awaited step (jg_step_node_awaited: checked, its bound taken), the rows it registers and the keys it cancels
-// (aw.ck of them: sorted, distinct), or null
+// (aw.ck of them: sorted, distinct), or null; `lookup`: the point query of a looked step (jg_step_node_looked: checked) and
+// its host list (lookup->listed), or null
 int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::NodePoll* poll, const jg_engine::NodeAwait* await,
-              const jg_await_row* await_rows, const uint64_t* await_keys) {
+              const jg_await_row* await_rows, const uint64_t* await_keys, const jg_engine::NodeLookup* lookup, const uint32_t* lookup_list) {
   static const bool trace = std::getenv("JG_TRACE_NODE") != nullptr;
   jg_engine::NodeStep& nd = e->node;
   NodeRun s;
@@ -443,6 +449,8 @@ int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::No
   o.poll = poll ? *poll : jg_engine::NodePoll{};
   o.aw = await ? *await : jg_engine::NodeAwait{};
   if (o.aw.on && (rc = node_await_stage(o, await_rows, await_keys))) return rc;  // (the rows are the caller's until here)
+  o.lk = lookup ? *lookup : jg_engine::NodeLookup{};
+  if (o.lk.on && (rc = node_lookup_stage(e, o, lookup_list))) return rc;  // (... and the list)
   if (s.keep) {  // (the set starts empty: its last step's regions went with that step's arena)
     o.set = e->cur_set, o.arena = e->cur_arena, o.irr_gen = e->irr_gen;
     o.d_fsm_cnt = nullptr, o.d_fsm = o.d_stage = nullptr, o.d_bsum = nullptr;
@@ -464,6 +472,7 @@ int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::No
   // the poll behind the step: gated by the step's own general-row count, final once the route pass has run (no rows: no gate)
   if (o.poll.want && (rc = node_poll_tail(e, o, s.n ? nd.d_nsparse : nullptr))) return rc;
   if (o.aw.on && (rc = node_await_tail(e, o, s.n ? nd.d_nsparse : nullptr))) return rc;
+  if (o.lk.on && (rc = node_lookup_tail(e, o, s.n ? nd.d_nsparse : nullptr))) return rc;
   if ((rc = node_publish(e, s, seq0, claim))) return rc;
   if (trace)
     std::fprintf(stderr, "[jg node] %zu rows: uploads + classify + route issued in %.0f us, waited %.0f us (H2D %.1f MB), halves + fsm build + outbox copies issued in %.0f us\n",
@@ -636,6 +645,10 @@ int node_settle(jg_engine* e) {
       o.aw.redone = true;
       if ((rc = node_await_tail(e, o, nullptr))) return rc;
     }
+    if (o.lk.on) {  // ... and its point query: the gated launch wrote no row
+      o.lk.redone = true;
+      if ((rc = node_lookup_tail(e, o, nullptr))) return rc;
+    }
     HIPCHK(hipEventRecord(o.ev_out, nd.down));
   }
   for (StepRec& rec : e->recs)
@@ -738,6 +751,7 @@ int node_keep_finish(jg_engine* e, jg_engine::NodeOut& o) {
   nd.fsm_guess = total, nd.fsm_guess_known = true;
   if ((rc = node_poll_finish(e, o))) return rc;  // (the rows its own copy did not bring: out of the arena, before it starts over)
   if ((rc = node_await_finish(e, o))) return rc;
+  if ((rc = node_lookup_finish(e, o))) return rc;
   // everything the step allocated has been read - d_stage just above was the last: its arena starts over, here and nowhere
   // else (records, if it had any, were drained above)
   e->arenas[o.arena].reset();

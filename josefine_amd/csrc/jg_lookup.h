@@ -14,6 +14,8 @@
 //                    16-byte stores - consecutive lanes, consecutive rows - and, asked for, R 8-byte progress heads.  An
 //                    index >= G (a device list: a host list is checked on the host) raises the call's error word with a
 //                    plain store and touches no column
+//   k_lookup_kept<R> the same body behind a kept node step (jg_step_node_looked): one scalar load of the step's general-row
+//                    count per workgroup; nonzero, no row is written and the verdict is left in a header word
 //   k_lookup_check   a device list longer than one staging piece: the bounds of every entry before the first piece is
 //                    made, so that nothing reaches the caller from a list that is refused
 //
@@ -38,9 +40,9 @@ struct JgLookupArgs {
   uint32_t* err;         // [1] set to 1 by an index >= G
 };
 
+// entry i of the list: the loads, the decode, the row and (asked for) the progress heads - the body of both kernels
 template <int R>
-__global__ __launch_bounds__(JG_BLOCK) void k_lookup(JgDev d, JgLookupArgs a) {
-  const uint32_t i = blockIdx.x * JG_BLOCK + threadIdx.x;
+__device__ __forceinline__ void jg_lookup_entry(const JgDev& d, const JgLookupArgs& a, uint32_t i) {
   if (i >= a.n) return;
   const uint32_t g = a.list ? a.list[i] : a.g0 + i;  // (uniform over the launch)
   if (g >= d.G) {
@@ -87,6 +89,27 @@ __global__ __launch_bounds__(JG_BLOCK) void k_lookup(JgDev d, JgLookupArgs a) {
       m[r] = !leader ? 0ull : jg_lag_wide(field, R) ? d.match_wide[(size_t)r * d.G + g] : base - field;
     }
   }
+}
+
+template <int R>
+__global__ __launch_bounds__(JG_BLOCK) void k_lookup(JgDev d, JgLookupArgs a) {
+  jg_lookup_entry<R>(d, a, blockIdx.x * JG_BLOCK + threadIdx.x);
+}
+
+// the lookup behind a kept node step (jg_step_node_looked).  `gate`: the step's general-row count on the device, or null.
+// Nonzero - the step is completed by a catch-up pass, the columns are not the settled state's yet - and the pass writes no
+// row: it leaves the verdict in hdr[JG_LH_GATE] and is queued once more, ungated, behind the catch-up pass.  Zero or null:
+// k_lookup, and a verdict of 0.
+#define JG_LH_GATE 0u   // the gate's verdict: the step's general-path rows as this pass saw them
+#define JG_LH_ERR 1u    // k_lookup's error word (a host list is checked on the host: stays 0)
+#define JG_LH_WORDS 2u
+
+template <int R>
+__global__ __launch_bounds__(JG_BLOCK) void k_lookup_kept(JgDev d, JgLookupArgs a, const uint32_t* gate, uint32_t* hdr) {
+  const uint32_t gated = gate ? *gate : 0u;  // (uniform: one scalar load per workgroup)
+  if (blockIdx.x == 0 && threadIdx.x == 0) hdr[JG_LH_GATE] = gated;
+  if (gated) return;
+  jg_lookup_entry<R>(d, a, blockIdx.x * JG_BLOCK + threadIdx.x);
 }
 
 __global__ __launch_bounds__(JG_BLOCK) void k_lookup_check(uint32_t G, const uint32_t* list, uint64_t n, uint32_t* err) {

@@ -429,7 +429,7 @@ class BatchedRaft(_Hosting):
 
     def step_node_begin(self, now_ms: int = 0, leader: bool = True, follower: bool = True, tick: bool = True, async_: bool = False,
                         common_ae: bool = False, fsm_fused: bool = False, keep: bool = False, poll: Optional[dict] = None,
-                        completions: Optional[dict] = None) -> None:
+                        completions: Optional[dict] = None, lookup: Optional[dict] = None) -> None:
         """jg_step_node alone (the outbox: `node_outbox`).  keep (JG_NODE_KEEP, with async_): the step keeps its outputs
         until its outbox is viewed - a second such step may be begun before that; `node_outbox` then serves the OLDER
         one and makes its rows the ones the next drains deliver.  poll (jg_step_node_polled, ABI v21; with keep): the
@@ -438,13 +438,29 @@ class BatchedRaft(_Hosting):
         ABI v23; with keep): dict(groups=, block_ids=, tokens=, terms=0, deadlines_ms=0, now_ms=, limit=None, peek=False,
         stats=False, cancel_keys=(), cancel_mask=2**64 - 1) - the waiters of `await_blocks` (optional: without them the
         step only watches) are registered, the cancel of `cancel_waiters` (ABI v24; optional) is made and the watch of
-        `watch_completions` is made behind the step; `node_completions` hands out the answer."""
+        `watch_completions` is made behind the step; `node_completions` hands out the answer.  lookup (jg_step_node_looked,
+        ABI v25; with keep): dict(groups=None, g0=0, n=None, progress=False), the arguments of `lookup` - the point query is
+        made behind the step, on the engine exactly as the step leaves it; `node_lookup` hands out the answer."""
         self._flush_pending()
         flags = (capi.NODE_LEADER_HALF if leader else 0) | (capi.NODE_FOLLOWER_HALF if follower else 0) | \
                 (capi.NODE_TICK if tick else 0) | (capi.NODE_ASYNC if async_ else 0) | \
                 (capi.NODE_COMMON_AE if common_ae else 0) | (capi.NODE_FSM_FUSED if fsm_fused else 0) | \
                 (capi.NODE_KEEP if keep else 0)
-        if completions is not None:
+        if lookup is not None:
+            if not hasattr(self.api, "step_node_looked"):
+                raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}step_node_looked")
+            p = held = req = rows = None
+            if poll is not None:
+                p, held, parts = self._poll_request(**poll)
+            if completions is not None:
+                req, rows, want_stats = self._await_request(**completions)
+            s, lst = self._lookup_set(**lookup)  # (`lst`: what s points at, alive over the call)
+            self._check(self.api.step_node_looked(self._h, int(now_ms), flags, C.byref(p) if p is not None else None,
+                                                  C.byref(req) if req is not None else None, C.byref(s)))
+            del held, lst
+            if completions is not None:
+                self._await_n = getattr(self, "_await_n", 0) + len(rows)
+        elif completions is not None:
             if not hasattr(self.api, "step_node_awaited"):
                 raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}step_node_awaited")
             p = held = None
@@ -875,6 +891,45 @@ class BatchedRaft(_Hosting):
         out = {name: int(getattr(c, name)) for name, t in capi.ReplCensus._fields_ if name not in per_member}
         for name in per_member:
             out[name] = [int(x) for x in getattr(c, name)[:self.R]]
+        return out
+
+    def _lookup_set(self, groups=None, g0: int = 0, n: Optional[int] = None, progress: bool = False):
+        """jg_group_set of a lookup from the arguments of `lookup`; with it the list it points at"""
+        s = capi.GroupSet()
+        if groups is None:
+            s.g0, s.n = int(g0), self.G - int(g0) if n is None else int(n)
+            lst = None
+        else:
+            g = np.asarray(groups if isinstance(groups, np.ndarray) else list(groups)).reshape(-1)
+            if g.size and (g.dtype.kind not in "iu" or int(g.min()) < 0 or int(g.max()) >= (1 << 32)):
+                raise EngineError(capi.EINVAL, "slot index out of range")
+            lst = np.ascontiguousarray(g, dtype=np.uint32)
+            s.n, s.groups = lst.size, lst.ctypes.data if lst.size else None
+        s.flags = capi.LOOKUP_PROGRESS if progress else 0
+        return s, lst
+
+    def node_lookup(self) -> dict:
+        """jg_node_lookup_view: the answer of the point query that travelled with the kept step whose outbox `node_outbox`
+        viewed last, as host copies: {"rows": what `lookup` returns for the same arguments (capi.GROUP_STATE_DTYPE),
+        "match": [n, R] with progress=True, "redone": the step had general-path rows and the pass ran behind its catch-up
+        pass (informational)}.  A step that carried no lookup: {"redone": False}."""
+        if not hasattr(self.api, "node_lookup_view"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}node_lookup_view")
+        v = capi.NodeLookup()
+        self._check(self.api.node_lookup_view(self._h, C.byref(v)))
+        if not v.attached:
+            return {"redone": False}
+        k = int(v.n)
+
+        def arr(p, dtype, shape):
+            if not k:
+                return np.zeros(shape, dtype)
+            nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+            return np.frombuffer((C.c_char * nbytes).from_address(p), dtype=dtype).reshape(shape).copy()
+
+        out = {"rows": arr(v.rows, capi.GROUP_STATE_DTYPE, (k,)), "redone": bool(v.state & capi.NODE_POLL_REDONE)}
+        if v.match:
+            out["match"] = arr(v.match, np.uint64, (k, self.R))
         return out
 
     def lookup(self, groups=None, g0: int = 0, n: Optional[int] = None, progress: bool = False):

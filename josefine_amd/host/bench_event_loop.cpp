@@ -235,6 +235,22 @@ static void run_loop(uint32_t G, uint32_t R, uint32_t T, uint32_t W, const std::
     if (poll_mode == "step") loop.set_poll(poll_q, poll_sink);
     uint64_t sink = 0, fsm_rows = 0, msg_rows = 0, col_bytes = 0, up_bytes = 0, general = 0;
     double t_sinks = 0;  // (inside the sinks: the consumers' reading of what came home - the rest of a step's time is the engine's calls and their waits)
+    // JG_BENCH_LOOKUP=<n> (off by default): a point query of n random partitions on every tick (BatchedEventLoop::lookup_async:
+    // with two ticks in flight the list travels with the tick's step - jg_step_node_looked - and the rows reach a sink with the
+    // tick's outputs; below that the synchronous lookup answers at the step boundary) - Metadata on every tick
+    const char* lookup_env = std::getenv("JG_BENCH_LOOKUP");
+    const uint32_t lookup_n = lookup_env ? (uint32_t)std::min(std::max(0, std::atoi(lookup_env)), (int)JG_NODE_LOOKUP_MAX) : 0u;
+    uint64_t lookups = 0, lookup_rows = 0, lookup_x = 0x9E3779B97F4A7C15ull + seed;
+    std::vector<uint32_t> lookup_list(lookup_n);
+    auto ask_lookup = [&] {
+      if (!lookup_n) return;
+      for (uint32_t& g : lookup_list) lookup_x ^= lookup_x << 13, lookup_x ^= lookup_x >> 7, lookup_x ^= lookup_x << 17, g = (uint32_t)(lookup_x % G);
+      loop.lookup_async(lookup_list, false, [&](const BatchedRaft::GroupStates& s, bool) {
+        const auto a = Clock::now();
+        sink += sum_words(s.rows.data(), s.rows.size() * sizeof(jg_group_state)), lookup_rows += s.rows.size(), lookups++;
+        t_sinks += ms_since(a);
+      });
+    };
     raft.fsm_rows_tx = [&](const jg_fsm_row* r, size_t n) {
       const auto a = Clock::now();
       sink += sum_split(r, n, sizeof(jg_fsm_row)), fsm_rows += n;
@@ -411,6 +427,7 @@ static void run_loop(uint32_t G, uint32_t R, uint32_t T, uint32_t W, const std::
         t_fill += ms_since(a), a = Clock::now();
         loop.tcp_rx_commit(G, 0, unchecked | (id32 ? (uint32_t)JG_COL_ID32 : 0u));
         t_submit += ms_since(a), a = Clock::now();
+        ask_lookup();
         loop.run_until(now);
         t_step += ms_since(a);
         rows_in += G - n;  // (n is added below: count the rows actually submitted)
@@ -427,6 +444,7 @@ static void run_loop(uint32_t G, uint32_t R, uint32_t T, uint32_t W, const std::
         loop.tcp_rx_commit(k, 0, (packed ? (uint32_t)JG_COL_PACKED_KIND : (uint32_t)(JG_COL_FROM | JG_COL_FLAG)) | (id32 ? (uint32_t)JG_COL_ID32 : 0u) | unchecked);
         const double ms_c = ms_since(a);
         t_submit += ms_c, a = Clock::now();
+        ask_lookup();
         loop.run_until(now);
         if (poll_mode == "sync") {
           loop.flush();
@@ -452,6 +470,7 @@ static void run_loop(uint32_t G, uint32_t R, uint32_t T, uint32_t W, const std::
       rows_in += n;
     }
     loop.flush();  // (pipelined: the last tick's outputs)
+    if (lookup_n) std::fprintf(stderr, "[lookup %u] %llu answers, %llu rows\n", lookup_n, (unsigned long long)lookups, (unsigned long long)lookup_rows);
     if (!poll_mode.empty()) std::fprintf(stderr, "[poll %s] %llu polls, %llu rows\n", poll_mode.c_str(), (unsigned long long)polls, (unsigned long long)poll_rows);
     const Clock::time_point t_end = rv.arrive();
     finished = true;

@@ -551,6 +551,42 @@ class BatchedRaft {
     if (redone) *redone = (v.state & JG_NODE_POLL_REDONE) != 0;
     return c;
   }
+  // Point queries behind a kept node step (jg_step_node_looked / jg_node_lookup_view, ABI v25; only callers need a library
+  // that has them): the step looks `groups` up (any order, repeats allowed, at most JG_NODE_LOOKUP_MAX), with `progress` the
+  // progress heads too, behind its own kernels and behind the poll `q` and the completion request `a` (null: not attached);
+  // node_lookup() hands the answer out once step_node_finish has served that step.  The answer is what lookup(groups, n,
+  // progress) would have returned between that step and the next.  The list is copied by the call.
+  void step_node_looked(uint64_t now_ms, uint32_t flags, const PollRequest* q, const AwaitRequest* a, const uint32_t* groups, size_t n,
+                        bool progress = false) {
+    flush_rows();
+    static const uint32_t none = 0;  // (an empty list is still a list)
+    jg_poll p{};
+    if (q) p = polled_words(*q);
+    jg_node_await_request w{};
+    if (a) {
+      w.rows = a->rows.data(), w.n = a->rows.size();
+      w.flags = a->peek ? (uint32_t)JG_WATCH_PEEK : 0u, w.want_stats = a->stats ? 1u : 0u;
+      w.now_ms = a->now_ms, w.cap = a->limit;
+      if (!a->cancel_keys.empty()) w.cancel_keys = a->cancel_keys.data(), w.cancel_n = a->cancel_keys.size(), w.cancel_mask = a->cancel_mask;
+    }
+    if (n > JG_NODE_LOOKUP_MAX) throw EngineError(JG_EINVAL, "step_node_looked: more than JG_NODE_LOOKUP_MAX entries");
+    jg_group_set s{};
+    s.n = (uint32_t)n, s.groups = n ? groups : &none, s.flags = progress ? (uint32_t)JG_LOOKUP_PROGRESS : 0u;
+    check(jg_step_node_looked(e_, now_ms, flags | (uint32_t)JG_NODE_ASYNC | (uint32_t)JG_NODE_KEEP, q ? &p : nullptr, a ? &w : nullptr, &s));
+    step_blocks_.emplace_back();
+    step_blocks_.back().swap(pending_blocks_);  // (as step_node_begin)
+  }
+  // the lookup of the kept step step_node_finish served last; *attached: that step carried one; *redone: JG_NODE_POLL_REDONE
+  GroupStates node_lookup(bool* attached = nullptr, bool* redone = nullptr) {
+    jg_node_lookup v{};
+    check(jg_node_lookup_view(e_, &v));
+    GroupStates out;
+    if (v.n) out.rows.assign(v.rows, v.rows + v.n);
+    if (v.n && v.match) out.match.assign(v.match, v.match + v.n * ids_.size());
+    if (attached) *attached = v.attached != 0;
+    if (redone) *redone = (v.state & JG_NODE_POLL_REDONE) != 0;
+    return out;
+  }
   // commit rows as the FSM rows a dense step does not queue: every row that is COMMITTED and not REWOUND becomes
   // JG_FSM_APPLY_LEADER (where LEADS: keys (a, b]) or JG_FSM_APPLY_FOLLOWER (keys [a, b)) {a = commit_from, b = commit}; a
   // rewound row has no range - the consumer resynchronises its store from the row's commit / head
@@ -1106,14 +1142,17 @@ class BatchedEventLoop {
   template <class Raft = BatchedRaft>
   void set_completions(CompletionSource source, CompletionSink sink, size_t limit = SIZE_MAX) {
     Raft* const r = &raft_;
-    begin_awaited_ = [this, r, source, limit](uint64_t at, uint32_t flags) {
-      typename Raft::AwaitRequest a;
+    fill_awaited_ = [this, source, limit](uint64_t at, BatchedRaft::AwaitRequest& a) {
       if (source) a.rows = source(at);
       a.now_ms = at, a.limit = limit;
       if (!cancels_.empty()) {  // cancel_tokens: the oldest key set travels with this step
         a.cancel_keys.swap(cancels_.front().first), a.cancel_mask = cancels_.front().second;
         cancels_.pop_front();
       }
+    };
+    begin_awaited_ = [this, r](uint64_t at, uint32_t flags) {
+      typename Raft::AwaitRequest a;
+      fill_awaited_(at, a);
       BatchedRaft::PollRequest qq;
       if (poll_q_) {
         qq = *poll_q_;
@@ -1125,6 +1164,74 @@ class BatchedEventLoop {
       bool attached = false, redone = false;
       const typename Raft::Completions c = r->node_completions(&attached, &redone);
       if (attached && sink) sink(c.rows, redone);
+    };
+  }
+
+  // Point queries from inside the loop (ABI v25; only a caller of lookup_async needs a library that has jg_step_node_looked /
+  // jg_node_lookup_view): the state of `groups` (any order, repeats allowed, at most JG_NODE_LOOKUP_MAX; with `progress` the
+  // progress heads too) - what Metadata, ListOffsets and a produce pre-check ask on a client connection.  Requests queue up.
+  // With in_flight >= 2 every tick's step carries the oldest one - and the ones behind it while their `progress` agrees and
+  // they fit JG_NODE_LOOKUP_MAX together, each sink getting its own slice - beside the poll of set_poll and the completion
+  // request of set_completions; the sink is called when that tick's outputs are consumed, after the poll's and the
+  // completions' sinks, with the partitions as that tick's step left them.  On a loop below two in flight no step is kept:
+  // the request is answered by the synchronous BatchedRaft::lookup at the next step boundary.
+  using LookupSink = std::function<void(const BatchedRaft::GroupStates&, bool redone)>;
+  template <class Raft = BatchedRaft>
+  void lookup_async(std::vector<uint32_t> groups, bool progress, LookupSink sink) {
+    if (groups.size() > JG_NODE_LOOKUP_MAX) throw EngineError(JG_EINVAL, "lookup_async: more than JG_NODE_LOOKUP_MAX entries");
+    lookups_.push_back(LookupAsk{std::move(groups), progress, std::move(sink)});
+    if (begin_looked_) return;
+    Raft* const r = &raft_;
+    begin_looked_ = [this, r](uint64_t at, uint32_t flags, bool awaited) {
+      // the oldest request and whoever behind it travels along
+      std::vector<uint32_t> list;
+      std::vector<LookupSlice> slices;
+      const bool progress = lookups_.front().progress;
+      size_t take = 0;
+      for (const LookupAsk& q : lookups_) {
+        if (take && (q.progress != progress || list.size() + q.groups.size() > JG_NODE_LOOKUP_MAX)) break;
+        slices.push_back(LookupSlice{list.size(), q.groups.size(), q.sink});
+        list.insert(list.end(), q.groups.begin(), q.groups.end());
+        take++;
+      }
+      typename Raft::AwaitRequest a;
+      if (awaited) fill_awaited_(at, a);
+      BatchedRaft::PollRequest qq;
+      if (poll_q_) {
+        qq = *poll_q_;
+        if (qq.timed) qq.clock.now_ms = at;
+      }
+      r->step_node_looked(at, flags, poll_q_ ? &qq : nullptr, awaited ? &a : nullptr, list.data(), list.size(), progress);
+      lookups_.erase(lookups_.begin(), lookups_.begin() + (std::ptrdiff_t)take);  // (a refused step keeps its requests queued)
+      looked_slices_.push_back(std::move(slices));
+    };
+    view_looked_ = [this, r]() {
+      bool attached = false, redone = false;
+      const typename Raft::GroupStates all = r->node_lookup(&attached, &redone);
+      std::vector<LookupSlice> slices;
+      slices.swap(looked_slices_.front());
+      looked_slices_.pop_front();
+      if (!attached) return;
+      const size_t R = all.rows.empty() ? 0 : all.match.size() / all.rows.size();
+      for (const LookupSlice& s : slices) {
+        if (!s.sink) continue;
+        if (slices.size() == 1) {
+          s.sink(all, redone);
+          continue;
+        }
+        typename Raft::GroupStates part;
+        part.rows.assign(all.rows.begin() + (std::ptrdiff_t)s.at, all.rows.begin() + (std::ptrdiff_t)(s.at + s.n));
+        if (R) part.match.assign(all.match.begin() + (std::ptrdiff_t)(s.at * R), all.match.begin() + (std::ptrdiff_t)((s.at + s.n) * R));
+        s.sink(part, redone);
+      }
+    };
+    sync_looked_ = [this, r]() {  // (nothing is outstanding: the synchronous call, request by request)
+      while (!lookups_.empty()) {
+        const LookupAsk q = std::move(lookups_.front());
+        lookups_.pop_front();
+        const typename Raft::GroupStates res = r->lookup(q.groups.data(), q.groups.size(), q.progress);
+        if (q.sink) q.sink(res, false);
+      }
     };
   }
 
@@ -1220,6 +1327,7 @@ class BatchedEventLoop {
     } else if (dense) {
       flush();
     }
+    if (!two && sync_looked_ && !lookups_.empty()) sync_looked_();  // (a step boundary of a loop that keeps no step)
     // (who THIS step's answers go to: noted per step, applied when the step is finished - with two ticks in flight the
     // step before is finished after this one has begun, and its answers go to the senders of ITS rows)
     std::vector<std::pair<uint32_t, NodeId>> answers;
@@ -1239,11 +1347,14 @@ class BatchedEventLoop {
       in_.clear();
       const bool awaited = two && begin_awaited_;  // (the step with both attachments, if there is a poll)
       const bool polled = two && (begin_polled_ || (awaited && poll_q_));
-      if (awaited) begin_awaited_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u));
+      const bool looked = two && begin_looked_ && !lookups_.empty();  // (... and the point queries that are waiting)
+      if (looked) begin_looked_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u), awaited);
+      else if (awaited) begin_awaited_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u));
       else if (polled) begin_polled_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u));
       else raft_.step_node_begin(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u), pipelined, two);
       polled_steps_.push_back(polled);
       awaited_steps_.push_back(awaited);
+      looked_steps_.push_back(looked);
       answers_of_step_.push_back(std::move(answers));  // (once the step has begun: one entry per open step, whatever begin() throws)
       last_at_ = at;
       if (pipelined) return;
@@ -1272,6 +1383,11 @@ class BatchedEventLoop {
       const bool awaited = awaited_steps_.front();
       awaited_steps_.pop_front();
       if (awaited) view_awaited_();
+    }
+    if (!looked_steps_.empty()) {
+      const bool looked = looked_steps_.front();
+      looked_steps_.pop_front();
+      if (looked) view_looked_();
     }
   }
   // Address::Local messages (server.rs:143) are applied before anything new is accepted
@@ -1346,6 +1462,22 @@ class BatchedEventLoop {
   std::function<void()> view_awaited_;                     // ... and its done rows to the sink
   std::deque<std::pair<std::vector<uint64_t>, uint64_t>> cancels_;  // cancel_tokens: (keys, mask) per awaited tick to come
   std::deque<bool> awaited_steps_;                         // per open step: was it begun with the completion request
+  std::function<void(uint64_t, BatchedRaft::AwaitRequest&)> fill_awaited_;  // set_completions: the request of the step beginning at a time
+  struct LookupAsk {
+    std::vector<uint32_t> groups;
+    bool progress;
+    LookupSink sink;
+  };
+  struct LookupSlice {
+    size_t at, n;  // the request's entries among the step's
+    LookupSink sink;
+  };
+  std::deque<LookupAsk> lookups_;                          // lookup_async: the requests no step carries yet, oldest first
+  std::function<void(uint64_t, uint32_t, bool)> begin_looked_;  // lookup_async: the step with the lookup (and the other requests) attached ...
+  std::function<void()> view_looked_;                      // ... its rows to the sinks ...
+  std::function<void()> sync_looked_;                      // ... and the requests of a loop that keeps no step, answered synchronously
+  std::deque<bool> looked_steps_;                          // per open step: was it begun with a lookup
+  std::deque<std::vector<LookupSlice>> looked_slices_;     // per looked step: whose entries are where
   std::deque<Message> local_;
   std::map<uint64_t, Response> requests_;
   std::map<std::pair<uint32_t, BlockId>, uint64_t> notifications_;
