@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define JG_ABI_VERSION 25u /* v25: jg_step_node_looked / jg_node_lookup_view, JG_NODE_LOOKUP_MAX (point queries behind a kept node step: Metadata with two ticks in flight); v24: jg_engine_await_cancel, jg_node_await_request.cancel_keys / cancel_n / cancel_mask, jg_node_await.marked, JG_DONE_CANCELLED (withdrawing waiters: a closed connection leaves the purgatory); v23: jg_step_node_awaited / jg_node_await_view (completions behind a kept node step: the purgatory with two ticks in flight); v22: jg_engine_await_open / jg_engine_await_blocks / jg_engine_watch_completions (the completion feed: fsm::Driver's notifications on the device); v21: jg_step_node_polled / jg_node_poll_view (a poll behind a kept node step: the feeds with two ticks in flight); v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
+#define JG_ABI_VERSION 26u /* v26: jg_step_node_hosted / jg_node_hosting_view, JG_NODE_HOSTING_MAX (opening and closing partitions behind a kept node step: LeaderAndIsr with two ticks in flight); v25: jg_step_node_looked / jg_node_lookup_view, JG_NODE_LOOKUP_MAX (point queries behind a kept node step: Metadata with two ticks in flight); v24: jg_engine_await_cancel, jg_node_await_request.cancel_keys / cancel_n / cancel_mask, jg_node_await.marked, JG_DONE_CANCELLED (withdrawing waiters: a closed connection leaves the purgatory); v23: jg_step_node_awaited / jg_node_await_view (completions behind a kept node step: the purgatory with two ticks in flight); v22: jg_engine_await_open / jg_engine_await_blocks / jg_engine_watch_completions (the completion feed: fsm::Driver's notifications on the device); v21: jg_step_node_polled / jg_node_poll_view (a poll behind a kept node step: the feeds with two ticks in flight); v20: jg_poll.clock (jg_engine_poll answers the replicas part under the time rule: the clocks advance in the one fused pass); v19: jg_engine_watch_replicas_timed (time-based in-sync sets: a per-replica clock in the replication feed); v18: jg_engine_poll (one poll per tick: the three change feeds and the two censuses in one call, one pass and one synchronisation); v17: jg_engine_watch_commits (the commit feed: what dense steps committed and appended); v16: jg_engine_lookup_groups (point queries: the state of a list of partitions in one call); v15: jg_engine_watch_replicas / jg_engine_replication_census (the replication feed: in-sync sets on the device); v14: jg_engine_watch_leaders / jg_engine_census (the leadership feed and the census); v13: vacant slots - jg_engine_open_groups / jg_engine_close_groups / jg_engine_list_groups, JG_CFG_START_VACANT, JG_FAULT_VACANT; v12: jg_engine_export_groups / jg_engine_import_groups (live groups handed between engines); v11: jg_engine_read_chains (the chain trees read back out, the inverse of v10); v10: jg_engine_load_chains (an engine opened on persisted chain trees); v9: JG_NODE_KEEP (two node steps in flight: jg_node_outbox_view serves the oldest); v8: jg_dense_cluster_round_routed delivers a partition's mail in the order (phase, emission index, sender) instead of
                              (sender, step, emission index) - same entry points, same layouts, different (legal) network schedule; v5: jg_step_node = arrival-order Apply (fsm_tx: Apply / Notify / Apply per partition), JG_CLUSTER_ANY_LEADER,
                              jg_dense_cluster_withdraw_appends, JG_COL_UNCHECKED, JG_COL_UPLOAD_NOW; v6: jg_dense_cluster_set_option, jg_dense_cluster_offer_appends, JG_CMD_RECREATE;
                              v7: the node step's bus formats - JG_COL_PACKED_KIND, JG_COL_ID32, JG_NODE_COMMON_AE (jg_node_outbox.aec), JG_NODE_FSM_FUSED (JG_FSM_LEADER_STEP) */
@@ -1394,6 +1394,65 @@ typedef struct jg_node_lookup {
   const uint64_t* match;              /* [n][R] progress heads, or NULL (JG_LOOKUP_PROGRESS not asked)      */
 } jg_node_lookup;
 int jg_node_lookup_view(jg_engine* e, jg_node_lookup* out);
+
+/* ---- opening and closing partitions behind a kept node step (ABI v26) -----------------------------
+ * jg_engine_open_groups and jg_engine_close_groups are refused while kept steps are outstanding or
+ * commands are queued, like every call that rewrites group state.  A HOSTED step carries a hosting
+ * request with it, as a polled step carries its poll, an awaited step its completion request and a looked
+ * step its point query: LeaderAndIsr, CreateTopics, DeleteTopics and the last step of a partition move
+ * without a bubble in a loop that always has a step outstanding - the next tick's rows may already
+ * address the slots this tick opens.
+ *
+ * CONTRACT.  Let S be the engine after kept step t is settled and before anything else touches it.  A
+ * step carrying a hosting request leaves the engine as jg_engine_close_groups(S, close) followed by
+ * jg_engine_open_groups(., now_ms, open) would, with the step's own now_ms: every column of every slot,
+ * the carried draw counts included.  The call defines no value of its own.  The two sets are independent,
+ * as two synchronous calls are: a set the synchronous call would refuse for a slot's state (opening a
+ * hosted slot, closing a vacant one) writes nothing, reports JG_NODE_HOSTING_CLOSE_REFUSED or
+ * JG_NODE_HOSTING_OPEN_REFUSED with the step's view and does not affect the other set.  The open's check
+ * sees the close's writes: a slot may be closed and reopened in one step.  The step's own outbox, drains,
+ * poll, completions and lookup all see S: the hosting pass is the last thing behind the step.  The feeds
+ * of step t + 1 see the change through the diff alone, as after the synchronous calls, and a waiter on a
+ * closed slot leaves as JG_DONE_VACANT at the next watch.  Rows of step t addressed to a slot it closes
+ * are applied first; rows of step t addressed to a slot it opens meet a vacant slot and are ignored; rows
+ * of step t + 1, submitted before step t is viewed, meet the opened slot.  The synchronous calls stay
+ * refused while kept steps are outstanding; once none is the two may be mixed freely.
+ *
+ * jg_step_node_hosted with hosting == NULL is exactly jg_step_node_looked(e, now_ms, flags, poll, await,
+ * lookup).  Otherwise the polled step's rules hold (JG_NODE_ASYNC | JG_NODE_KEEP, no multi-device
+ * parent), and both sets, their host lists and self_slots are copied at entry: the caller's memory is free
+ * when the call returns.  Either set may be NULL.  Accepted per set: a range (groups == NULL: g0, n - any
+ * length within G) or a host list, strictly ascending, of at most JG_NODE_HOSTING_MAX entries; on the open
+ * set self_slots (with a list or a range of at most JG_NODE_HOSTING_MAX entries).  Refused with JG_EINVAL:
+ * an unknown flag, JG_GROUPS_DEVICE (a device list's bounds are known only on the device, and a refusal
+ * that arrives a tick late is not worth having), a longer list, an index >= G, a range out of bounds, a
+ * list that is not strictly ascending, self_slots[i] >= R, self_slots on the close set.  Every argument -
+ * `poll`, `await` and `lookup` by their own rules - is checked before anything of the step is queued: a
+ * refused call steps nothing and leaves the submitted rows queued.  The state check (open needs vacant,
+ * close needs hosted) is made on the device, behind the step, and arrives with the view: vacancy is the
+ * device's knowledge.  A set with n == 0 is attached and writes nothing.  The poll, the completion request
+ * and the lookup, if attached, are queued first.
+ *
+ * jg_node_hosting_view answers for the kept step whose outbox jg_node_outbox_view finished last;
+ * JG_EINVAL if no kept step has been viewed yet.  attached == 0: that step carried no hosting request
+ * (JG_OK, everything else 0).  closed / opened: the slots each set wrote - its n, or 0 when it was refused
+ * (or NULL).  state: JG_NODE_POLL_REDONE as for the poll - the step had general-path rows, the passes
+ * behind its first pass wrote nothing (the device saw the count) and ran once more behind the catch-up
+ * pass - and the two *_REFUSED bits. */
+enum { JG_NODE_HOSTING_MAX = 65536u }; /* entries of a host list (or of self_slots) a step can carry */
+enum { JG_NODE_HOSTING_CLOSE_REFUSED = 2u, JG_NODE_HOSTING_OPEN_REFUSED = 4u }; /* jg_node_hosting.state, beside JG_NODE_POLL_REDONE */
+typedef struct jg_node_hosting_request {
+  const jg_group_set* close;          /* may be NULL: made first                                            */
+  const jg_group_set* open;           /* may be NULL: made at the step's now_ms                             */
+} jg_node_hosting_request;
+typedef struct jg_node_hosting {
+  uint32_t attached, state;           /* 1: the step carried a request; JG_NODE_POLL_REDONE, JG_NODE_HOSTING_*_REFUSED */
+  uint32_t closed, opened;            /* slots written by each set: its n, or 0                             */
+} jg_node_hosting;
+int jg_step_node_hosted(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_poll* poll /* may be NULL */,
+                        const jg_node_await_request* await /* may be NULL */, const jg_group_set* lookup /* may be NULL */,
+                        const jg_node_hosting_request* hosting /* may be NULL */);
+int jg_node_hosting_view(jg_engine* e, jg_node_hosting* out);
 
 /* ---- a closed loop of dense node ticks ------------------------------------------------------------
  * All R nodes of every partition in ONE process (one engine per node, e.g. the three brokers of

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 CLUSTER_ANY_LEADER = 0xFFFFFFFF
 CLUSTER_OPT_VOTE_WORDS = 1
 MAX_REPLICAS = 8
@@ -310,6 +310,20 @@ class NodeLookup(C.Structure):
     _fields_ = [("attached", C.c_uint32), ("state", C.c_uint32), ("rows", C.c_void_p), ("n", C.c_size_t), ("match", C.c_void_p)]
 
 
+NODE_HOSTING_MAX = 65536  # jg_step_node_hosted: the most entries of a host list (or of self_slots) a step can carry
+NODE_HOSTING_CLOSE_REFUSED, NODE_HOSTING_OPEN_REFUSED = 2, 4  # jg_node_hosting.state, beside NODE_POLL_REDONE
+
+
+class NodeHostingRequest(C.Structure):
+    """jg_node_hosting_request."""
+    _fields_ = [("close", C.c_void_p), ("open", C.c_void_p)]
+
+
+class NodeHosting(C.Structure):
+    """jg_node_hosting."""
+    _fields_ = [("attached", C.c_uint32), ("state", C.c_uint32), ("closed", C.c_uint32), ("opened", C.c_uint32)]
+
+
 # mailbox words (josefine_gpu.h: JG_ANSWER / JG_AE)
 MAILBOX_NONE = (1 << 56) - 1
 
@@ -462,6 +476,9 @@ class Api:
         "node_await_view": (C.c_int, [_P, C.POINTER(NodeAwait)]),
         "step_node_looked": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.POINTER(Poll), C.POINTER(NodeAwaitRequest), C.POINTER(GroupSet)]),
         "node_lookup_view": (C.c_int, [_P, C.POINTER(NodeLookup)]),
+        "step_node_hosted": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.POINTER(Poll), C.POINTER(NodeAwaitRequest), C.POINTER(GroupSet),
+                                       C.POINTER(NodeHostingRequest)]),
+        "node_hosting_view": (C.c_int, [_P, C.POINTER(NodeHosting)]),
     }
     # only the oracle has these
     _ORACLE_PROTOS = {
@@ -516,4 +533,5 @@ HEADER_SYMBOLS = [
     "jg_step_node_awaited", "jg_node_await_view",
     "jg_engine_await_cancel",
     "jg_step_node_looked", "jg_node_lookup_view",
+    "jg_step_node_hosted", "jg_node_hosting_view",
 ]

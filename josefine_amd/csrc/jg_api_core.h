@@ -464,6 +464,23 @@ struct jg_engine {
     char* scratch = nullptr;           // the set's arena: the list, the rows, the progress heads, the header words
     bool redone = false;               // queued once more, ungated, behind the catch-up pass (JG_NODE_POLL_REDONE)
   };
+  // the hosting request of a kept node step: what the set keeps of its two jg_group_set, and the step's own bookkeeping
+  struct NodeHostSet {
+    uint32_t g0 = 0, n = 0;            // the range (listed == false), the entries
+    bool listed = false, own = false;  // a host list / self_slots, staged in NodeOut::l_hosting_up at `up_list` / `up_self`
+    size_t up_list = 0, up_self = 0;
+  };
+  struct NodeHosting {
+    bool on = false;                   // the step carries a hosting request
+    NodeHostSet close, open;
+    size_t staged = 0;                 // bytes of NodeOut::l_hosting_up the two sets take
+    uint32_t own_mask = 0;             // the own slots the open's self_slots name (none: every opened slot keeps its own)
+    uint64_t now = 0;                  // the step's now_ms: the opened slots' election timers start here
+    uint32_t seq = 0;                  // the engine's step number as the step leaves it (the pass behind the catch-up pass: the same)
+    int self0 = 0;                     // e->uniform_self as the step began: what its own kernels and its catch-up pass assume
+    char* scratch = nullptr;           // the set's arena: the header words, the lists, the own slots
+    bool redone = false;               // queued once more, ungated, behind the catch-up pass (JG_NODE_POLL_REDONE)
+  };
   struct NodeOut {
     jg_leader_beat* h_beat = nullptr;  // pinned mirrors of the outbox columns
     uint64_t *h_ae = nullptr, *h_answer = nullptr, *h_hbc = nullptr, *h_aec = nullptr;
@@ -512,6 +529,11 @@ struct jg_engine {
     PinnedQueue<char> l_lookup_up;     // pinned: the step's staged list on its way up (bytes)
     PinnedQueue<char> l_lookup;        // pinned: where the rows, the progress heads and the header words land (bytes); sized at entry
     jg_node_lookup lookup_view{};      // what jg_node_lookup_view hands out once the step's outbox has been viewed
+    // -- jg_step_node_hosted: the hosting request that travels with the step (jg_api_hosting.h) ---------------------------
+    NodeHosting hs;                    // the two sets as copied at entry (on == false: the step carries none)
+    PinnedQueue<char> l_hosting_up;    // pinned: the step's staged lists and own slots on their way up (bytes)
+    PinnedQueue<char> l_hosting;       // pinned: where the two sets' header words land (bytes)
+    jg_node_hosting hosting_view{};    // what jg_node_hosting_view hands out once the step's outbox has been viewed
   };
   struct NodeStep {
     // The two sets.  `newest` is the one the newest step took (a kept step takes the other one, a plain step the same one

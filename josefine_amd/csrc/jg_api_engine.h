@@ -225,6 +225,7 @@ void jg_engine_destroy(jg_engine* e) {
     for (PinnedQueue<char>& q : o.l_poll) q.destroy();
     o.l_await_up.destroy(), o.l_await.destroy();
     o.l_lookup_up.destroy(), o.l_lookup.destroy();
+    o.l_hosting_up.destroy(), o.l_hosting.destroy();
   }
   if (e->node.ev_cols) (void)hipEventDestroy(e->node.ev_cols);
   e->q_msgs.destroy();

@@ -2,6 +2,12 @@
 // Open and close go through jg_api_manage.h's check_then_write: a check pass writes an error word, the host reads it, and
 // only then does the write pass run.  The scratch (a host list and its own slots, the error words; the list passes'
 // workgroup counts and output) is carved from the engine's staging.  Part of josefine_gpu.hip's one translation unit.
+//
+// And jg_step_node_hosted / jg_node_hosting_view (ABI v26): the hosting request that travels with a kept node step, as the
+// poll, the completion request and the point query do - node_hosting_check by the entry point (jg_api_poll.h), then
+// node_hosting_stage / node_hosting_tail / node_hosting_finish, called by jg_api_node.h.  No host read sits between a check
+// pass and its write pass there: the kept kernels run under the step's general-row gate, the write pass looks at the error
+// word itself, and four header words per set travel home with the step.
 #pragma once
 
 namespace {
@@ -156,9 +162,144 @@ int list_shard(jg_engine* e, uint32_t which, uint32_t g0, uint32_t n, uint32_t a
   return JG_OK;
 }
 
+// ---- hosting behind a kept node step (jg_step_node_hosted) --------------------------------------------------------------
+
+// the rules of jg_step_node_hosted for one set of the request on a single-device engine; `hs`: what the step's set keeps
+int node_hosting_check_set(const jg_engine* e, const jg_group_set* s, bool open, jg_engine::NodeHostSet& hs, uint32_t& own_mask) {
+  const uint32_t G = e->cfg.n_groups, R = e->cfg.n_replicas;
+  const std::string w = open ? "jg_step_node_hosted: open: " : "jg_step_node_hosted: close: ";
+  hs = jg_engine::NodeHostSet{};
+  if (!s) return JG_OK;
+  if (s->flags & ~(uint32_t)JG_GROUPS_DEVICE) return fail(JG_EINVAL, w + "unknown flag");
+  if (s->flags & JG_GROUPS_DEVICE) return fail(JG_EINVAL, w + "a device list's bounds are known only on the device: a host list or a range");
+  if (!open && s->self_slots) return fail(JG_EINVAL, w + "self_slots is for opening");
+  if ((s->groups || s->self_slots) && s->n > JG_NODE_HOSTING_MAX) return fail(JG_EINVAL, w + "more than JG_NODE_HOSTING_MAX listed entries");
+  if (!s->groups && (uint64_t)s->g0 + s->n > G) return fail(JG_EINVAL, w + "slot range out of bounds");
+  if (s->groups)
+    for (uint32_t i = 0; i < s->n; i++) {
+      if (s->groups[i] >= G) return fail(JG_EINVAL, w + "a slot index is out of range (nothing was stepped)");
+      if (i && s->groups[i - 1] >= s->groups[i]) return fail(JG_EINVAL, w + "the list is not strictly ascending (nothing was stepped)");
+    }
+  if (s->self_slots)
+    for (uint32_t i = 0; i < s->n; i++) {
+      if (s->self_slots[i] >= R) return fail(JG_EINVAL, w + "an own slot >= n_replicas (nothing was stepped)");
+      own_mask |= 1u << s->self_slots[i];
+    }
+  hs.g0 = s->groups ? 0u : s->g0, hs.n = s->n;
+  hs.listed = s->groups != nullptr && s->n, hs.own = s->self_slots != nullptr && s->n;
+  return JG_OK;
+}
+
+int node_hosting_check(const jg_engine* e, const jg_node_hosting_request* req, jg_engine::NodeHosting& hs) {
+  hs = jg_engine::NodeHosting{};
+  if (const int rc = node_hosting_check_set(e, req->close, false, hs.close, hs.own_mask)) return rc;
+  if (const int rc = node_hosting_check_set(e, req->open, true, hs.open, hs.own_mask)) return rc;
+  hs.on = true;
+  return JG_OK;
+}
+
+// where the sets' header words land in the set's pinned area: the close's, then the open's
+#define NODE_HOSTING_LAND (2u * JG_HH_WORDS * 4u)
+
+// the step's lists and own slots into the set's pinned staging (the set is the step's from here on: whatever read it last
+// has been viewed); the landing area preset to ones - a header that never arrives is a gated one
+int node_hosting_stage(jg_engine* e, jg_engine::NodeOut& o, const jg_node_hosting_request* req) {
+  (void)e;
+  jg_engine::NodeHosting& hs = o.hs;
+  Carve c;
+  if (hs.close.listed) hs.close.up_list = c.sect((size_t)hs.close.n * 4);
+  if (hs.open.listed) hs.open.up_list = c.sect((size_t)hs.open.n * 4);
+  if (hs.open.own) hs.open.up_self = c.sect(hs.open.n);
+  hs.staged = c.at;
+  o.l_hosting_up.n = o.l_hosting.n = 0;
+  HIPCHK(o.l_hosting.reserve(NODE_HOSTING_LAND));
+  std::memset(o.l_hosting.p, 0xff, NODE_HOSTING_LAND);
+  if (c.at) HIPCHK(o.l_hosting_up.reserve(c.at));
+  char* const U = o.l_hosting_up.p;
+  if (hs.close.listed) std::memcpy(U + hs.close.up_list, req->close->groups, (size_t)hs.close.n * 4);
+  if (hs.open.listed) std::memcpy(U + hs.open.up_list, req->open->groups, (size_t)hs.open.n * 4);
+  if (hs.open.own) std::memcpy(U + hs.open.up_self, req->open->self_slots, hs.open.n);
+  return JG_OK;
+}
+
+// The hosting request of kept step `o`, queued behind every kernel of that step that is in the stream by now - its poll's,
+// its completion request's, its lookup's - and the header words' trip home on the down stream: check + close, then check +
+// open, so that the open's check sees the close's writes; each write pass returns where its check raised the error word.
+// Scratch - header words, lists, own slots - is the set's arena's.  The pass behind the catch-up pass uses the same block and
+// the step's own step number.  `gate`: as for node_poll_tail.  Synchronises nothing.
+int node_hosting_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate) {
+  jg_engine::NodeStep& nd = e->node;
+  jg_engine::NodeHosting& hs = o.hs;
+  if (!hs.close.n && !hs.open.n) return JG_OK;
+  const size_t staged = hs.staged;
+  if (!hs.scratch) {  // (the block: the header words first, then the staging as it was carved)
+    HIPCHK(e->arenas[o.arena].alloc(NODE_HOSTING_LAND + staged, (void**)&hs.scratch));
+    hs.seq = e->seq;
+  }
+  char* const B = hs.scratch;
+  char* const L = B + NODE_HOSTING_LAND;
+  uint32_t* const hdr = (uint32_t*)B;
+  if (!hs.redone && staged) HIPCHK(hipMemcpyAsync(L, o.l_hosting_up.p, staged, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemsetAsync(hdr, 0, NODE_HOSTING_LAND, e->stream));  // (the error words are only ever raised, the written words only set)
+  for (int open = 0; open < 2; open++) {
+    const jg_engine::NodeHostSet& s = open ? hs.open : hs.close;
+    if (!s.n) continue;
+    uint32_t* const h = hdr + (open ? JG_HH_WORDS : 0u);
+    JgGroupsArgs a{};
+    a.g0 = s.g0, a.n = s.n, a.open = (uint32_t)open, a.seq = hs.seq, a.now = hs.now;
+    a.list = s.listed ? (const uint32_t*)(L + s.up_list) : nullptr;
+    a.self = s.own ? (const uint8_t*)(L + s.up_self) : nullptr;
+    a.err = h + JG_HH_ERR;
+    const dim3 grid((s.n + JG_BLOCK - 1) / JG_BLOCK), block(JG_BLOCK);
+    hipLaunchKernelGGL(k_groups_check_kept, grid, block, 0, e->stream, e->dev, a, gate, h);
+    if (open) hipLaunchKernelGGL(k_groups_open_kept, grid, block, 0, e->stream, e->dev, a, gate, h);
+    else hipLaunchKernelGGL(k_groups_close_kept, grid, block, 0, e->stream, e->dev, a, gate, h);
+    HIPCHK(hipGetLastError());
+    e->n_launch += 2;
+  }
+  HIPCHK(hipEventRecord(o.ev_kernels, e->stream));
+  HIPCHK(hipStreamWaitEvent(nd.down, o.ev_kernels, 0));
+  HIPCHK(hipMemcpyAsync(o.l_hosting.p, hdr, NODE_HOSTING_LAND, hipMemcpyDeviceToHost, nd.down));
+  return JG_OK;
+}
+
+// Kept step `o` is being viewed and its outputs have landed: the header words say what each set did - a pass that was gated
+// and never queued again did nothing and says so - and become what jg_node_hosting_view hands out.  Before the set's arena
+// starts over.
+int node_hosting_finish(jg_engine* e, jg_engine::NodeOut& o) {
+  (void)e;
+  jg_engine::NodeHosting& hs = o.hs;
+  jg_node_hosting& v = o.hosting_view;
+  v = jg_node_hosting{};
+  if (!hs.on) return JG_OK;
+  hs.scratch = nullptr;  // (the arena's: gone with it)
+  v.attached = 1u, v.state = hs.redone ? (uint32_t)JG_NODE_POLL_REDONE : 0u;
+  const uint32_t* const land = (const uint32_t*)o.l_hosting.p;
+  for (int open = 0; open < 2; open++) {
+    const jg_engine::NodeHostSet& s = open ? hs.open : hs.close;
+    if (!s.n) continue;
+    const uint32_t* const h = land + (open ? JG_HH_WORDS : 0u);
+    if (h[JG_HH_GATE]) return fail(JG_EDEVICE, "internal: a hosted step's pass was gated and not queued again");
+    const uint32_t x = h[JG_HH_ERR];
+    if (x & (JG_HOST_E_RANGE | JG_HOST_E_ORDER | JG_HOST_E_SLOT)) return fail(JG_EDEVICE, "internal: a hosted step's set failed on the device a check made at entry");
+    if (x & JG_HOST_E_DEFER) return fail(JG_EDEVICE, "internal: a hosted step met per-step deferral bits of a listed slot behind the settled step");
+    if (x & JG_HOST_E_STATE) v.state |= open ? (uint32_t)JG_NODE_HOSTING_OPEN_REFUSED : (uint32_t)JG_NODE_HOSTING_CLOSE_REFUSED;
+    (open ? v.opened : v.closed) = h[JG_HH_WRITTEN];
+  }
+  return JG_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int jg_node_hosting_view(jg_engine* e, jg_node_hosting* out) {
+  if (!e || !out) return fail(JG_EINVAL, "null argument");
+  if (e->router) return fail(JG_EINVAL, "jg_node_hosting_view: a hosted step is a shard's (jg_get_shard)");
+  if (e->node.poll_viewed < 0) return fail(JG_EINVAL, "jg_node_hosting_view: no kept step's outbox has been viewed (or a newer step has claimed its set)");
+  *out = e->node.sets[e->node.poll_viewed].hosting_view;
+  return JG_OK;
+}
 
 int jg_engine_open_groups(jg_engine* e, uint64_t now_ms, const jg_group_set* s) { return groups_call(e, true, now_ms, s); }
 

@@ -168,7 +168,7 @@ int check_then_write(jg_engine* e, Make make, Check check, Write write) {
 // flag words changed under the dense path's feet, so the device's irregular_seen word is re-read at the next
 // synchronisation; and every group has the one own slot `uniform_self`, or the engine stops assuming one
 // (own_slots: the mask of the own slots written; 0 when none were).
-void groups_rewritten(jg_engine* e, uint32_t own_slots = 0) {
+void groups_rewritten(jg_engine* e, uint32_t own_slots) {
   e->stepped = true;
   e->maybe_irregular = true;
   e->flag_check_pending = true;

@@ -117,6 +117,12 @@ int node_await_finish(jg_engine* e, jg_engine::NodeOut& o);
 int node_lookup_stage(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* list);
 int node_lookup_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate);
 int node_lookup_finish(jg_engine* e, jg_engine::NodeOut& o);
+// (jg_api_hosting.h) the hosting request that travels with a kept step: its lists and own slots staged at entry, its check
+// and write passes queued last behind the step's kernels, its verdict collected when the step's outbox is viewed
+int node_hosting_stage(jg_engine* e, jg_engine::NodeOut& o, const jg_node_hosting_request* req);
+int node_hosting_tail(jg_engine* e, jg_engine::NodeOut& o, const uint32_t* gate);
+int node_hosting_finish(jg_engine* e, jg_engine::NodeOut& o);
+void groups_rewritten(jg_engine* e, uint32_t own_slots = 0);  // (jg_api_manage.h)
 
 // node_step (or node_settle's catch-up pass) is running: its halves' own node_settle calls are not another caller's
 struct InStep {
@@ -428,9 +434,11 @@ int node_publish(jg_engine* e, const NodeRun& s, uint32_t seq0, NodeClaim& claim
 // `poll`: the request of a polled step (jg_step_node_polled: checked, and a kept step's), or null; `await`: the completion
 // request of an awaited step (jg_step_node_awaited: checked, its bound taken), the rows it registers and the keys it cancels
 // (aw.ck of them: sorted, distinct), or null; `lookup`: the point query of a looked step (jg_step_node_looked: checked) and
-// its host list (lookup->listed), or null
+// its host list (lookup->listed), or null; `hosting`: the hosting request of a hosted step (jg_step_node_hosted: checked) and
+// the caller's two sets, whose lists and own slots are copied here, or null
 int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::NodePoll* poll, const jg_engine::NodeAwait* await,
-              const jg_await_row* await_rows, const uint64_t* await_keys, const jg_engine::NodeLookup* lookup, const uint32_t* lookup_list) {
+              const jg_await_row* await_rows, const uint64_t* await_keys, const jg_engine::NodeLookup* lookup, const uint32_t* lookup_list,
+              const jg_engine::NodeHosting* hosting, const jg_node_hosting_request* hosting_req) {
   static const bool trace = std::getenv("JG_TRACE_NODE") != nullptr;
   jg_engine::NodeStep& nd = e->node;
   NodeRun s;
@@ -451,6 +459,9 @@ int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::No
   if (o.aw.on && (rc = node_await_stage(o, await_rows, await_keys))) return rc;  // (the rows are the caller's until here)
   o.lk = lookup ? *lookup : jg_engine::NodeLookup{};
   if (o.lk.on && (rc = node_lookup_stage(e, o, lookup_list))) return rc;  // (... and the list)
+  o.hs = hosting ? *hosting : jg_engine::NodeHosting{};
+  if (o.hs.on && (rc = node_hosting_stage(e, o, hosting_req))) return rc;  // (... and the two sets' lists and own slots)
+  o.hs.now = now_ms, o.hs.self0 = e->uniform_self;
   if (s.keep) {  // (the set starts empty: its last step's regions went with that step's arena)
     o.set = e->cur_set, o.arena = e->cur_arena, o.irr_gen = e->irr_gen;
     o.d_fsm_cnt = nullptr, o.d_fsm = o.d_stage = nullptr, o.d_bsum = nullptr;
@@ -473,7 +484,13 @@ int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::No
   if (o.poll.want && (rc = node_poll_tail(e, o, s.n ? nd.d_nsparse : nullptr))) return rc;
   if (o.aw.on && (rc = node_await_tail(e, o, s.n ? nd.d_nsparse : nullptr))) return rc;
   if (o.lk.on && (rc = node_lookup_tail(e, o, s.n ? nd.d_nsparse : nullptr))) return rc;
+  // the hosting pass is the last thing behind the step: whatever the step itself answers has seen the engine without it
+  if (o.hs.on && (rc = node_hosting_tail(e, o, s.n ? nd.d_nsparse : nullptr))) return rc;
   if ((rc = node_publish(e, s, seq0, claim))) return rc;
+  // what a rewrite of group state owes the engine's summaries of it, from the NEXT step on: this step's status block was
+  // taken before the pass and its irr_gen at the claim, so it settles no flag; its catch-up pass assumes o.hs.self0.
+  // (Conservative where the device refuses a set: the host cannot know yet.)
+  if (o.hs.on && (o.hs.close.n || o.hs.open.n)) groups_rewritten(e, o.hs.own_mask);
   if (trace)
     std::fprintf(stderr, "[jg node] %zu rows: uploads + classify + route issued in %.0f us, waited %.0f us (H2D %.1f MB), halves + fsm build + outbox copies issued in %.0f us\n",
                  s.n, s.T1 - s.T0, s.T2 - s.T1, s.bytes_up / 1e6, node_clk() - s.T2);
@@ -622,6 +639,13 @@ int node_settle(jg_engine* e) {
   if (o.keep) HIPCHK(hipStreamSynchronize(e->stream));
   InStep in_step(nd.in_step);
   int rc = JG_OK;
+  // (a hosted step: the kernels of its catch-up pass assume the own slot its first pass assumed - its opens come behind them)
+  struct OwnSlot {
+    int& now;
+    const int after;
+    OwnSlot(int& v, int during) : now(v), after(v) { now = during; }
+    ~OwnSlot() { now = after; }
+  } own_slot(e->uniform_self, o.keep && o.hs.on ? o.hs.self0 : e->uniform_self);
   const uint32_t seq_end = e->seq;
   e->seq = pd.seq_general;
   const size_t recs_before = e->recs.size();
@@ -648,6 +672,10 @@ int node_settle(jg_engine* e) {
     if (o.lk.on) {  // ... and its point query: the gated launch wrote no row
       o.lk.redone = true;
       if ((rc = node_lookup_tail(e, o, nullptr))) return rc;
+    }
+    if (o.hs.on) {  // ... and, last, its hosting request: the gated passes wrote nothing
+      o.hs.redone = true;
+      if ((rc = node_hosting_tail(e, o, nullptr))) return rc;
     }
     HIPCHK(hipEventRecord(o.ev_out, nd.down));
   }
@@ -752,6 +780,7 @@ int node_keep_finish(jg_engine* e, jg_engine::NodeOut& o) {
   if ((rc = node_poll_finish(e, o))) return rc;  // (the rows its own copy did not bring: out of the arena, before it starts over)
   if ((rc = node_await_finish(e, o))) return rc;
   if ((rc = node_lookup_finish(e, o))) return rc;
+  if ((rc = node_hosting_finish(e, o))) return rc;
   // everything the step allocated has been read - d_stage just above was the last: its arena starts over, here and nowhere
   // else (records, if it had any, were drained above)
   e->arenas[o.arena].reset();

@@ -10,9 +10,9 @@
 // jg_node_poll_view (ABI v21): the same chain queued BEHIND a kept node step over scratch of the step's own arena, gated on
 // the device by the step's general-row count, its header and rows sent home on the step's trip and handed out when the
 // step's outbox is viewed (node_poll_tail, node_poll_finish: called by jg_api_node.h).  And jg_step_node_awaited /
-// jg_node_await_view (ABI v23) and jg_step_node_looked (ABI v25): the one entry point of a kept step with attachments - the
-// poll, the completion request of jg_api_await.h, the point query of jg_api_lookup.h, or any of them together.  Part of
-// josefine_gpu.hip's one translation unit.
+// jg_node_await_view (ABI v23), jg_step_node_looked (ABI v25) and jg_step_node_hosted (ABI v26): the one entry point of a kept
+// step with attachments - the poll, the completion request of jg_api_await.h, the point query of jg_api_lookup.h, the hosting
+// request of jg_api_hosting.h, or any of them together.  Part of josefine_gpu.hip's one translation unit.
 #pragma once
 
 namespace {
@@ -483,14 +483,19 @@ int jg_step_node_awaited(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg
 
 int jg_step_node_looked(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_poll* request, const jg_node_await_request* await,
                         const jg_group_set* lookup) {
-  if (!request && !await && !lookup) return jg_step_node(e, now_ms, flags);
-  const char* const who = lookup ? "jg_step_node_looked" : await ? "jg_step_node_awaited" : "jg_step_node_polled";
+  return jg_step_node_hosted(e, now_ms, flags, request, await, lookup, nullptr);
+}
+
+int jg_step_node_hosted(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_poll* request, const jg_node_await_request* await,
+                        const jg_group_set* lookup, const jg_node_hosting_request* hosting) {
+  if (!request && !await && !lookup && !hosting) return jg_step_node(e, now_ms, flags);
+  const char* const who = hosting ? "jg_step_node_hosted" : lookup ? "jg_step_node_looked" : await ? "jg_step_node_awaited" : "jg_step_node_polled";
   if (!e) return fail(JG_EINVAL, "null argument");
   if (!(flags & (JG_NODE_LEADER_HALF | JG_NODE_FOLLOWER_HALF)) || (flags & ~127u))
     return fail(JG_EINVAL, std::string(who) + ": flags = JG_NODE_LEADER_HALF and / or JG_NODE_FOLLOWER_HALF [| JG_NODE_TICK] | JG_NODE_ASYNC [| JG_NODE_COMMON_AE] [| JG_NODE_FSM_FUSED] | JG_NODE_KEEP");
   if (e->router) return fail(JG_EINVAL, std::string(who) + ": a polled or awaited step is a shard's (jg_get_shard): JG_NODE_KEEP is per shard");
   if (!(flags & JG_NODE_KEEP) || !(flags & JG_NODE_ASYNC))
-    return fail(JG_EINVAL, std::string(who) + ": a poll, a completion request and a lookup travel with a kept step: JG_NODE_ASYNC | JG_NODE_KEEP");
+    return fail(JG_EINVAL, std::string(who) + ": a poll, a completion request, a lookup and a hosting request travel with a kept step: JG_NODE_ASYNC | JG_NODE_KEEP");
   if (request)
     if (const int rc = poll_check(e, request, false)) return rc;
   jg_engine::NodeAwait aw;  // (*await: copied here; its rows and keys once the step has its set - node_await_stage)
@@ -513,6 +518,9 @@ int jg_step_node_looked(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_
   jg_engine::NodeLookup lk;  // (*lookup: copied here; its host list once the step has its set - node_lookup_stage)
   if (lookup)
     if (const int rc = node_lookup_check(e, lookup, lk)) return rc;
+  jg_engine::NodeHosting hs;  // (*hosting: copied here; its lists and own slots once the step has its set - node_hosting_stage)
+  if (hosting)
+    if (const int rc = node_hosting_check(e, hosting, hs)) return rc;
   if (e->inflight.phase) return fail(JG_EINVAL, "a drain is in transfer: jg_drain_wait first");
   jg_engine::NodePoll np;  // (*request and *request->clock: copied here)
   if (request) {
@@ -528,7 +536,7 @@ int jg_step_node_looked(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_
     np.pol = request->policy, np.lag_limit = request->census_lag_limit;
   }
   return node_step(e, now_ms, flags, request ? &np : nullptr, await ? &aw : nullptr, await ? await->rows : nullptr, keys.data(),
-                   lookup ? &lk : nullptr, lookup ? lookup->groups : nullptr);
+                   lookup ? &lk : nullptr, lookup ? lookup->groups : nullptr, hosting ? &hs : nullptr, hosting);
 }
 
 int jg_node_await_view(jg_engine* e, jg_node_await* out) {

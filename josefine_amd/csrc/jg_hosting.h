@@ -10,6 +10,9 @@
 //                    JG_CMD_RECREATE row does), the own slot first; returns at once when the error word is set
 //   k_groups_close   the write pass of a close: the canonical vacant record through jg_store plus the columns a follower's
 //                    jg_store leaves alone (packed progress, wide progress, window segments, foreign voters)
+//   k_groups_check_kept / k_groups_open_kept / k_groups_close_kept
+//                    the same three bodies behind a kept node step (jg_step_node_hosted): one scalar load of the step's
+//                    general-row count per workgroup; nonzero, nothing is read or written but the verdict in a header word
 //   k_list_count     stream compaction over the flag column (the skeleton of both passes: jg_compact.h), pass 1: per
 //                    workgroup the number of matching slots (a 64-bit __ballot and a __popcll per wave and row of 256 slots)
 //   k_scan_block_sums (jg_sparse.h) the workgroup counts -> exclusive prefixes and the total
@@ -51,7 +54,9 @@ __device__ __forceinline__ uint32_t jg_wave_or(uint32_t v) {
   return v;
 }
 
-__global__ __launch_bounds__(JG_BLOCK) void k_groups_check(JgDev d, JgGroupsArgs a) {
+// this lane's entry of a set, checked - the body of k_groups_check and k_groups_check_kept (every lane of a workgroup calls
+// it; the arguments by value: by reference the compiler schedules k_groups_check differently from the kernel it was)
+__device__ __forceinline__ void jg_groups_check_entry(JgDev d, JgGroupsArgs a) {
   const uint32_t i = blockIdx.x * JG_BLOCK + threadIdx.x;
   uint32_t e = 0, slots = 0;
   if (i < a.n) {
@@ -79,7 +84,12 @@ __global__ __launch_bounds__(JG_BLOCK) void k_groups_check(JgDev d, JgGroupsArgs
   }
 }
 
-__global__ __launch_bounds__(JG_BLOCK) void k_groups_open(JgDev d, JgGroupsArgs a) {
+__global__ __launch_bounds__(JG_BLOCK) void k_groups_check(JgDev d, JgGroupsArgs a) {
+  jg_groups_check_entry(d, a);
+}
+
+// this lane's entry of an open, written - the body of k_groups_open and k_groups_open_kept
+__device__ __forceinline__ void jg_groups_open_entry(const JgDev& d, const JgGroupsArgs& a) {
   if (*(volatile uint32_t*)a.err) return;  // refused: nothing is written
   const uint32_t i = blockIdx.x * JG_BLOCK + threadIdx.x;
   if (i >= a.n) return;
@@ -93,7 +103,12 @@ __global__ __launch_bounds__(JG_BLOCK) void k_groups_open(JgDev d, JgGroupsArgs 
   jg_store<false>(d, L);
 }
 
-__global__ __launch_bounds__(JG_BLOCK) void k_groups_close(JgDev d, JgGroupsArgs a) {
+__global__ __launch_bounds__(JG_BLOCK) void k_groups_open(JgDev d, JgGroupsArgs a) {
+  jg_groups_open_entry(d, a);
+}
+
+// this lane's entry of a close, written - the body of k_groups_close and k_groups_close_kept
+__device__ __forceinline__ void jg_groups_close_entry(const JgDev& d, const JgGroupsArgs& a) {
   if (*(volatile uint32_t*)a.err) return;
   const uint32_t i = blockIdx.x * JG_BLOCK + threadIdx.x;
   if (i >= a.n) return;
@@ -123,6 +138,42 @@ __global__ __launch_bounds__(JG_BLOCK) void k_groups_close(JgDev d, JgGroupsArgs
     d.win_next[(size_t)w * G + g] = 0;
   }
   for (uint32_t v = 0; v < JG_FOREIGN_VOTERS; v++) d.fvote_id[(size_t)v * G + g] = 0;
+}
+
+__global__ __launch_bounds__(JG_BLOCK) void k_groups_close(JgDev d, JgGroupsArgs a) {
+  jg_groups_close_entry(d, a);
+}
+
+// Hosting behind a kept node step (jg_step_node_hosted): per set four header words, a.err == hdr + JG_HH_ERR.  `gate`: the
+// step's general-row count on the device, or null.  Nonzero - the step is completed by a catch-up pass, the columns are not
+// the settled state's yet - and no lane loads or stores anything: lane 0 of workgroup 0 leaves the verdict in hdr[JG_HH_GATE]
+// and the three launches are queued once more, ungated, behind the catch-up pass.  Zero or null: the plain kernels' bodies,
+// the write pass returning where the check pass raised the error word - no host read sits between the two.
+#define JG_HH_GATE 0u     // the gate's verdict: the step's general-path rows as the check pass saw them
+#define JG_HH_ERR 1u      // JG_HOST_E_* bits (JgGroupsArgs::err[0])
+#define JG_HH_SLOTS 2u    // the own slots an open writes (JgGroupsArgs::err[1])
+#define JG_HH_WRITTEN 3u  // the slots the write pass wrote: n, or 0 (refused, or gated)
+#define JG_HH_WORDS 4u
+
+__global__ __launch_bounds__(JG_BLOCK) void k_groups_check_kept(JgDev d, JgGroupsArgs a, const uint32_t* gate, uint32_t* hdr) {
+  const uint32_t gated = gate ? *gate : 0u;  // (uniform: one scalar load per workgroup)
+  if (blockIdx.x == 0 && threadIdx.x == 0) hdr[JG_HH_GATE] = gated;
+  if (gated) return;
+  jg_groups_check_entry(d, a);
+}
+
+__global__ __launch_bounds__(JG_BLOCK) void k_groups_open_kept(JgDev d, JgGroupsArgs a, const uint32_t* gate, uint32_t* hdr) {
+  const uint32_t gated = gate ? *gate : 0u;
+  if (gated) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) hdr[JG_HH_WRITTEN] = *(volatile uint32_t*)a.err ? 0u : a.n;
+  jg_groups_open_entry(d, a);
+}
+
+__global__ __launch_bounds__(JG_BLOCK) void k_groups_close_kept(JgDev d, JgGroupsArgs a, const uint32_t* gate, uint32_t* hdr) {
+  const uint32_t gated = gate ? *gate : 0u;
+  if (gated) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) hdr[JG_HH_WRITTEN] = *(volatile uint32_t*)a.err ? 0u : a.n;
+  jg_groups_close_entry(d, a);
 }
 
 struct JgListArgs {

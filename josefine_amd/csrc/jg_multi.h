@@ -258,7 +258,8 @@ int router_step(jg_engine* p, uint64_t now_ms) {
 
 int node_step(jg_engine* e, uint64_t now_ms, uint32_t flags, const jg_engine::NodePoll* poll, const jg_engine::NodeAwait* await = nullptr,
               const jg_await_row* await_rows = nullptr, const uint64_t* await_keys = nullptr, const jg_engine::NodeLookup* lookup = nullptr,
-              const uint32_t* lookup_list = nullptr);
+              const uint32_t* lookup_list = nullptr, const jg_engine::NodeHosting* hosting = nullptr,
+              const jg_node_hosting_request* hosting_req = nullptr);
 
 // jg_step_node on every shard (each one's rows were bucketed by jg_submit)
 int router_step_node(jg_engine* p, uint64_t now_ms, uint32_t flags) {

@@ -429,7 +429,7 @@ class BatchedRaft(_Hosting):
 
     def step_node_begin(self, now_ms: int = 0, leader: bool = True, follower: bool = True, tick: bool = True, async_: bool = False,
                         common_ae: bool = False, fsm_fused: bool = False, keep: bool = False, poll: Optional[dict] = None,
-                        completions: Optional[dict] = None, lookup: Optional[dict] = None) -> None:
+                        completions: Optional[dict] = None, lookup: Optional[dict] = None, hosting: Optional[dict] = None) -> None:
         """jg_step_node alone (the outbox: `node_outbox`).  keep (JG_NODE_KEEP, with async_): the step keeps its outputs
         until its outbox is viewed - a second such step may be begun before that; `node_outbox` then serves the OLDER
         one and makes its rows the ones the next drains deliver.  poll (jg_step_node_polled, ABI v21; with keep): the
@@ -440,23 +440,35 @@ class BatchedRaft(_Hosting):
         step only watches) are registered, the cancel of `cancel_waiters` (ABI v24; optional) is made and the watch of
         `watch_completions` is made behind the step; `node_completions` hands out the answer.  lookup (jg_step_node_looked,
         ABI v25; with keep): dict(groups=None, g0=0, n=None, progress=False), the arguments of `lookup` - the point query is
-        made behind the step, on the engine exactly as the step leaves it; `node_lookup` hands out the answer."""
+        made behind the step, on the engine exactly as the step leaves it; `node_lookup` hands out the answer.  hosting
+        (jg_step_node_hosted, ABI v26; with keep): dict(close=None, open=None, self_slots=None) - `close` and `open` as the
+        `groups` of `close_groups` and `open_groups` (an iterable of slot indices or a range), `self_slots` the open's own
+        slots: behind everything else of the step the engine becomes what close_groups(close) and then
+        open_groups(open, now_ms, self_slots) make of it; `node_hosting` hands out the verdict."""
         self._flush_pending()
         flags = (capi.NODE_LEADER_HALF if leader else 0) | (capi.NODE_FOLLOWER_HALF if follower else 0) | \
                 (capi.NODE_TICK if tick else 0) | (capi.NODE_ASYNC if async_ else 0) | \
                 (capi.NODE_COMMON_AE if common_ae else 0) | (capi.NODE_FSM_FUSED if fsm_fused else 0) | \
                 (capi.NODE_KEEP if keep else 0)
-        if lookup is not None:
-            if not hasattr(self.api, "step_node_looked"):
-                raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}step_node_looked")
-            p = held = req = rows = None
+        if lookup is not None or hosting is not None:
+            entry = "step_node_looked" if hosting is None else "step_node_hosted"
+            if not hasattr(self.api, entry):
+                raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}{entry}")
+            p = held = req = rows = s = lst = None
             if poll is not None:
                 p, held, parts = self._poll_request(**poll)
             if completions is not None:
                 req, rows, want_stats = self._await_request(**completions)
-            s, lst = self._lookup_set(**lookup)  # (`lst`: what s points at, alive over the call)
-            self._check(self.api.step_node_looked(self._h, int(now_ms), flags, C.byref(p) if p is not None else None,
-                                                  C.byref(req) if req is not None else None, C.byref(s)))
+            if lookup is not None:
+                s, lst = self._lookup_set(**lookup)  # (`lst`: what s points at, alive over the call)
+            args = (self._h, int(now_ms), flags, C.byref(p) if p is not None else None, C.byref(req) if req is not None else None,
+                    C.byref(s) if s is not None else None)
+            if hosting is None:
+                self._check(self.api.step_node_looked(*args))
+            else:
+                hr, sets = self._hosting_request(**hosting)  # (`sets`: what hr points at, alive over the call)
+                self._check(self.api.step_node_hosted(*args, C.byref(hr)))
+                del sets
             del held, lst
             if completions is not None:
                 self._await_n = getattr(self, "_await_n", 0) + len(rows)
@@ -892,6 +904,33 @@ class BatchedRaft(_Hosting):
         for name in per_member:
             out[name] = [int(x) for x in getattr(c, name)[:self.R]]
         return out
+
+    def _hosting_request(self, close=None, open=None, self_slots=None):  # noqa: A002 (the header's name)
+        """jg_node_hosting_request from the arguments of `close_groups` and `open_groups`; with it what it points at"""
+        if self_slots is not None and open is None:
+            raise EngineError(capi.EINVAL, "hosting: self_slots is for opening")
+        hr, keep = capi.NodeHostingRequest(), []
+        for field, groups, own in (("close", close, None), ("open", open, self_slots)):
+            if groups is None:
+                continue
+            gs = self._group_set(groups, own, False, keep)
+            keep.append(gs)
+            setattr(hr, field, C.addressof(gs))
+        return hr, keep
+
+    def node_hosting(self) -> dict:
+        """jg_node_hosting_view: the verdict of the hosting request that travelled with the kept step whose outbox
+        `node_outbox` viewed last: {"redone": the step had general-path rows and the passes ran behind its catch-up pass
+        (informational), "closed" / "opened": the slots each set wrote (its length, or 0), "close_refused" / "open_refused":
+        the set met a slot in the wrong state and wrote nothing}.  A step that carried no request: {"redone": False}."""
+        if not hasattr(self.api, "node_hosting_view"):
+            raise EngineError(capi.EINVAL, f"{self.api.path} does not export {self.api.prefix}node_hosting_view")
+        v = capi.NodeHosting()
+        self._check(self.api.node_hosting_view(self._h, C.byref(v)))
+        if not v.attached:
+            return {"redone": False}
+        return {"redone": bool(v.state & capi.NODE_POLL_REDONE), "closed": int(v.closed), "opened": int(v.opened),
+                "close_refused": bool(v.state & capi.NODE_HOSTING_CLOSE_REFUSED), "open_refused": bool(v.state & capi.NODE_HOSTING_OPEN_REFUSED)}
 
     def _lookup_set(self, groups=None, g0: int = 0, n: Optional[int] = None, progress: bool = False):
         """jg_group_set of a lookup from the arguments of `lookup`; with it the list it points at"""

@@ -587,6 +587,83 @@ class BatchedRaft {
     if (redone) *redone = (v.state & JG_NODE_POLL_REDONE) != 0;
     return out;
   }
+  // Partitions opened and closed behind a kept node step (jg_step_node_hosted / jg_node_hosting_view, ABI v26; only callers
+  // need a library that has them): behind everything else of the step - its own kernels, the poll `q`, the completion
+  // request `a`, the lookup (`looked`: of `groups`, as step_node_looked) - the engine becomes what close_groups(h.close) and
+  // then open_groups(h.open, now_ms, h.self_slots) make of it; each list strictly ascending, at most JG_NODE_HOSTING_MAX
+  // entries.  A set the synchronous call would refuse for a slot's state writes nothing and does not affect the other.
+  // node_hosting() hands the verdict out once step_node_finish has served that step; step_node_finish itself applies to this
+  // mirror what the sets wrote, behind the step's own blocks - the stores of closed and opened partitions start over, a
+  // closed partition's queued tokens and proposals are dropped.  The lists are copied by the call.
+  struct Hosting {
+    bool has_close = false, has_open = false, has_self = false;
+    std::vector<uint32_t> close, open;
+    std::vector<uint8_t> self_slots;  // has_self: one own slot per entry of `open`
+  };
+  struct HostingVerdict {
+    bool attached = false, redone = false, close_refused = false, open_refused = false;
+    uint32_t closed = 0, opened = 0;  // the slots each set wrote: its length, or 0
+  };
+  void step_node_hosted(uint64_t now_ms, uint32_t flags, const PollRequest* q, const AwaitRequest* a, bool looked, const uint32_t* groups, size_t n,
+                        bool progress, const Hosting& h) {
+    flush_rows();
+    static const uint32_t none = 0;  // (an empty list is still a list)
+    jg_poll p{};
+    if (q) p = polled_words(*q);
+    jg_node_await_request w{};
+    if (a) {
+      w.rows = a->rows.data(), w.n = a->rows.size();
+      w.flags = a->peek ? (uint32_t)JG_WATCH_PEEK : 0u, w.want_stats = a->stats ? 1u : 0u;
+      w.now_ms = a->now_ms, w.cap = a->limit;
+      if (!a->cancel_keys.empty()) w.cancel_keys = a->cancel_keys.data(), w.cancel_n = a->cancel_keys.size(), w.cancel_mask = a->cancel_mask;
+    }
+    if (looked && n > JG_NODE_LOOKUP_MAX) throw EngineError(JG_EINVAL, "step_node_hosted: more than JG_NODE_LOOKUP_MAX entries");
+    if (h.close.size() > JG_NODE_HOSTING_MAX || h.open.size() > JG_NODE_HOSTING_MAX) throw EngineError(JG_EINVAL, "step_node_hosted: more than JG_NODE_HOSTING_MAX entries");
+    if (h.has_self && h.self_slots.size() != h.open.size()) throw EngineError(JG_EINVAL, "step_node_hosted: one own slot per opened slot");
+    jg_group_set s{}, sc{}, so{};
+    s.n = (uint32_t)n, s.groups = n ? groups : &none, s.flags = progress ? (uint32_t)JG_LOOKUP_PROGRESS : 0u;
+    sc.n = (uint32_t)h.close.size(), sc.groups = sc.n ? h.close.data() : &none;
+    so.n = (uint32_t)h.open.size(), so.groups = so.n ? h.open.data() : &none;
+    so.self_slots = h.has_self && so.n ? h.self_slots.data() : nullptr;
+    jg_node_hosting_request r{};
+    r.close = h.has_close ? &sc : nullptr, r.open = h.has_open ? &so : nullptr;
+    const size_t ordinal = steps_finished_ + step_blocks_.size();
+    check(jg_step_node_hosted(e_, now_ms, flags | (uint32_t)JG_NODE_ASYNC | (uint32_t)JG_NODE_KEEP, q ? &p : nullptr, a ? &w : nullptr,
+                              looked ? &s : nullptr, &r));
+    step_blocks_.emplace_back();
+    step_blocks_.back().swap(pending_blocks_);  // (as step_node_begin)
+    hosted_.push_back({ordinal, h});
+    if (!follow_hosting_)  // (set here, so that only a program that begins hosted steps names jg_node_hosting_view)
+      follow_hosting_ = [this]() {
+        jg_node_hosting v{};
+        check(jg_node_hosting_view(e_, &v));
+        const Hosting h = std::move(hosted_.front().second);
+        hosted_.pop_front();
+        if (v.closed)
+          for (uint32_t g : h.close) {
+            stores_[g] = BlockStore{};
+            queued_[g].clear();
+            extend_failed_.erase(g);
+            pending_reqs_.erase(pending_reqs_.lower_bound({g, 0}), pending_reqs_.lower_bound({g + 1, 0}));
+          }
+        if (v.opened)
+          for (uint32_t g : h.open) {
+            stores_[g] = BlockStore{};
+            stores_[g].insert(Block{0, 0, {}});
+            extend_failed_.erase(g);
+          }
+      };
+  }
+  // the verdict of the kept step step_node_finish served last (attached == false: it carried no hosting request)
+  HostingVerdict node_hosting() {
+    jg_node_hosting v{};
+    check(jg_node_hosting_view(e_, &v));
+    HostingVerdict out;
+    out.attached = v.attached != 0, out.redone = (v.state & JG_NODE_POLL_REDONE) != 0;
+    out.close_refused = (v.state & JG_NODE_HOSTING_CLOSE_REFUSED) != 0, out.open_refused = (v.state & JG_NODE_HOSTING_OPEN_REFUSED) != 0;
+    out.closed = v.closed, out.opened = v.opened;
+    return out;
+  }
   // commit rows as the FSM rows a dense step does not queue: every row that is COMMITTED and not REWOUND becomes
   // JG_FSM_APPLY_LEADER (where LEADS: keys (a, b]) or JG_FSM_APPLY_FOLLOWER (keys [a, b)) {a = commit_from, b = commit}; a
   // rewound row has no range - the consumer resynchronises its store from the row's commit / head
@@ -674,6 +751,7 @@ class BatchedRaft {
   }
   double ms_waited_for_outputs = 0;  // inside jg_node_outbox_view, summed over the steps finished so far (a loop's own accounting)
   bool node_step_open() const { return !step_blocks_.empty(); }
+  size_t replicas() const { return ids_.size(); }
   size_t node_steps_open() const { return step_blocks_.size(); }
   void step_node_finish(const std::vector<NodeId>* answers_to = nullptr) {
     if (step_blocks_.empty()) return;
@@ -685,8 +763,10 @@ class BatchedRaft {
     // (what was noted since begin() - an AppendEntries submitted meanwhile - belongs to a later step: it waits for that one)
     std::vector<std::pair<uint32_t, Block>> later = std::move(step_blocks_.front());
     step_blocks_.pop_front();
+    steps_finished_++;
     later.swap(pending_blocks_);
     after_step();  // (stores this step's blocks and leaves none pending)
+    if (!hosted_.empty() && hosted_.front().first + 1 == steps_finished_) follow_hosting_();  // (a hosted step: what it closed and opened, behind its own blocks)
     pending_blocks_.insert(pending_blocks_.begin(), std::make_move_iterator(later.begin()), std::make_move_iterator(later.end()));
     if (columns_tx) columns_tx(o);
     else if (rpc_tx) expand_columns(o, answers_to);
@@ -957,6 +1037,9 @@ class BatchedRaft {
   std::vector<uint64_t> term_, id_, aux_, blk_id_, blk_next_;
   std::vector<std::pair<uint32_t, Block>> pending_blocks_;
   std::deque<std::vector<std::pair<uint32_t, Block>>> step_blocks_;  // one entry per node step begun and not finished (oldest first)
+  size_t steps_finished_ = 0;                           // node steps step_node_finish has served
+  std::deque<std::pair<size_t, Hosting>> hosted_;       // step_node_hosted: (which step, its sets) until step_node_finish has served that step
+  std::function<void()> follow_hosting_;                // ... and what the mirror owes the oldest of them then
   std::set<uint32_t> extend_failed_;  // partitions whose process died in Chain::extend (until their restart)
   std::map<std::pair<uint32_t, uint64_t>, std::vector<uint8_t>> pending_reqs_;
 };
@@ -1183,17 +1266,10 @@ class BatchedEventLoop {
     if (begin_looked_) return;
     Raft* const r = &raft_;
     begin_looked_ = [this, r](uint64_t at, uint32_t flags, bool awaited) {
-      // the oldest request and whoever behind it travels along
       std::vector<uint32_t> list;
       std::vector<LookupSlice> slices;
-      const bool progress = lookups_.front().progress;
-      size_t take = 0;
-      for (const LookupAsk& q : lookups_) {
-        if (take && (q.progress != progress || list.size() + q.groups.size() > JG_NODE_LOOKUP_MAX)) break;
-        slices.push_back(LookupSlice{list.size(), q.groups.size(), q.sink});
-        list.insert(list.end(), q.groups.begin(), q.groups.end());
-        take++;
-      }
+      bool progress = false;
+      const size_t take = gather_lookups(list, slices, progress);
       typename Raft::AwaitRequest a;
       if (awaited) fill_awaited_(at, a);
       BatchedRaft::PollRequest qq;
@@ -1233,6 +1309,30 @@ class BatchedEventLoop {
         if (q.sink) q.sink(res, false);
       }
     };
+  }
+
+  // Partitions opened and closed from inside the loop (ABI v26; only a caller of open_async / close_async needs a library that
+  // has jg_step_node_hosted / jg_node_hosting_view): what LeaderAndIsr, CreateTopics, DeleteTopics and the last step of a
+  // partition move do in a running broker.  `groups` strictly ascending, at most JG_NODE_HOSTING_MAX; `self_slots` empty (every
+  // slot keeps its own) or one own slot per group.  Requests queue up.  With in_flight >= 2 every tick's step carries the
+  // oldest close and the oldest open - the close is made first, so a step may close and reopen a slot - beside the poll, the
+  // completion request and the point queries; a sink is called when that tick's outputs are consumed, after the lookups'
+  // sinks, the two of one step in the order they were asked: applied == false - a listed slot was in the wrong state, the
+  // set wrote nothing.  Rows for a slot that a tick opens may be handed to the loop from the next tick on.  On a loop below
+  // two in flight no step is kept: the requests are made by the synchronous BatchedRaft::close_groups / open_groups at the
+  // next step boundary, in the order they were asked - applied == false, as from a step, where a listed slot is in the wrong
+  // state (the loop asks first); anything else that refuses the synchronous call throws out of run_until.  A request the
+  // step could not carry is refused by open_async / close_async themselves: a list too long, not ascending or out of range,
+  // an own slot >= the number of replicas.
+  using HostingSink = std::function<void(bool applied, bool redone)>;
+  template <class Raft = BatchedRaft>
+  void open_async(std::vector<uint32_t> groups, std::vector<uint8_t> self_slots, HostingSink sink) {
+    if (!self_slots.empty() && self_slots.size() != groups.size()) throw EngineError(JG_EINVAL, "open_async: one own slot per group, or none");
+    hosting_ask<Raft>(opens_, "open_async", std::move(groups), std::move(self_slots), std::move(sink));
+  }
+  template <class Raft = BatchedRaft>
+  void close_async(std::vector<uint32_t> groups, HostingSink sink) {
+    hosting_ask<Raft>(closes_, "close_async", std::move(groups), {}, std::move(sink));
   }
 
   // Withdraw waiters from inside the loop (ABI v24; with set_completions): the keys are attached to the next awaited tick's
@@ -1328,6 +1428,7 @@ class BatchedEventLoop {
       flush();
     }
     if (!two && sync_looked_ && !lookups_.empty()) sync_looked_();  // (a step boundary of a loop that keeps no step)
+    if (!two && sync_hosted_ && (!closes_.empty() || !opens_.empty())) sync_hosted_(at);
     // (who THIS step's answers go to: noted per step, applied when the step is finished - with two ticks in flight the
     // step before is finished after this one has begun, and its answers go to the senders of ITS rows)
     std::vector<std::pair<uint32_t, NodeId>> answers;
@@ -1348,13 +1449,16 @@ class BatchedEventLoop {
       const bool awaited = two && begin_awaited_;  // (the step with both attachments, if there is a poll)
       const bool polled = two && (begin_polled_ || (awaited && poll_q_));
       const bool looked = two && begin_looked_ && !lookups_.empty();  // (... and the point queries that are waiting)
-      if (looked) begin_looked_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u), awaited);
+      const bool hosted = two && begin_hosted_ && (!closes_.empty() || !opens_.empty());  // (... and the oldest close and open)
+      if (hosted) begin_hosted_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u), awaited, looked);
+      else if (looked) begin_looked_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u), awaited);
       else if (awaited) begin_awaited_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u));
       else if (polled) begin_polled_(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u));
       else raft_.step_node_begin(at, halves | bus | (tick ? (uint32_t)JG_NODE_TICK : 0u), pipelined, two);
       polled_steps_.push_back(polled);
       awaited_steps_.push_back(awaited);
       looked_steps_.push_back(looked);
+      hosted_steps_.push_back(hosted);
       answers_of_step_.push_back(std::move(answers));  // (once the step has begun: one entry per open step, whatever begin() throws)
       last_at_ = at;
       if (pipelined) return;
@@ -1388,6 +1492,11 @@ class BatchedEventLoop {
       const bool looked = looked_steps_.front();
       looked_steps_.pop_front();
       if (looked) view_looked_();
+    }
+    if (!hosted_steps_.empty()) {
+      const bool hosted = hosted_steps_.front();
+      hosted_steps_.pop_front();
+      if (hosted) view_hosted_();
     }
   }
   // Address::Local messages (server.rs:143) are applied before anything new is accepted
@@ -1478,6 +1587,109 @@ class BatchedEventLoop {
   std::function<void()> sync_looked_;                      // ... and the requests of a loop that keeps no step, answered synchronously
   std::deque<bool> looked_steps_;                          // per open step: was it begun with a lookup
   std::deque<std::vector<LookupSlice>> looked_slices_;     // per looked step: whose entries are where
+  struct HostingAsk {
+    uint64_t asked;  // the request's number among the loop's hosting requests
+    std::vector<uint32_t> groups;
+    std::vector<uint8_t> self_slots;
+    HostingSink sink;
+  };
+  struct HostedStep {
+    bool has_close = false, has_open = false;
+    uint64_t close_asked = 0, open_asked = 0;
+    HostingSink close, open;
+  };
+  std::deque<HostingAsk> closes_, opens_;                  // close_async / open_async: the requests no step carries yet, oldest first
+  uint64_t hosting_asked_ = 0;
+  std::function<void(uint64_t, uint32_t, bool, bool)> begin_hosted_;  // open_async / close_async: the step with the hosting request (and the other requests) attached ...
+  std::function<void()> view_hosted_;                      // ... its verdict to the sinks ...
+  std::function<void(uint64_t)> sync_hosted_;              // ... and the requests of a loop that keeps no step, made synchronously
+  std::deque<bool> hosted_steps_;                          // per open step: was it begun with a hosting request
+  std::deque<HostedStep> hosted_sinks_;                    // per hosted step: who hears of which set
+  // lookup_async: the oldest request and whoever behind it travels along - their entries into `list`, who gets which into
+  // `slices`; returns how many requests these are (they stay queued: a refused step keeps them)
+  size_t gather_lookups(std::vector<uint32_t>& list, std::vector<LookupSlice>& slices, bool& progress) const {
+    progress = lookups_.front().progress;
+    size_t take = 0;
+    for (const LookupAsk& q : lookups_) {
+      if (take && (q.progress != progress || list.size() + q.groups.size() > JG_NODE_LOOKUP_MAX)) break;
+      slices.push_back(LookupSlice{list.size(), q.groups.size(), q.sink});
+      list.insert(list.end(), q.groups.begin(), q.groups.end());
+      take++;
+    }
+    return take;
+  }
+  // open_async / close_async: the request checked (what would refuse the step that carries it refuses the call) and queued
+  template <class Raft>
+  void hosting_ask(std::deque<HostingAsk>& queue, const char* who, std::vector<uint32_t> groups, std::vector<uint8_t> self_slots, HostingSink sink) {
+    if (groups.size() > JG_NODE_HOSTING_MAX) throw EngineError(JG_EINVAL, (std::string(who) + ": more than JG_NODE_HOSTING_MAX entries").c_str());
+    for (size_t i = 0; i < groups.size(); i++)
+      if (groups[i] >= G_ || (i && groups[i - 1] >= groups[i])) throw EngineError(JG_EINVAL, (std::string(who) + ": slot indices strictly ascending and within the engine").c_str());
+    for (uint8_t s : self_slots)
+      if (s >= raft_.replicas()) throw EngineError(JG_EINVAL, (std::string(who) + ": an own slot >= the number of replicas").c_str());
+    queue.push_back(HostingAsk{hosting_asked_++, std::move(groups), std::move(self_slots), std::move(sink)});
+    if (begin_hosted_) return;
+    Raft* const r = &raft_;
+    begin_hosted_ = [this, r](uint64_t at, uint32_t flags, bool awaited, bool looked) {
+      std::vector<uint32_t> list;
+      std::vector<LookupSlice> slices;
+      bool progress = false;
+      const size_t take = looked ? gather_lookups(list, slices, progress) : 0;
+      typename Raft::AwaitRequest a;
+      if (awaited) fill_awaited_(at, a);
+      BatchedRaft::PollRequest qq;
+      if (poll_q_) {
+        qq = *poll_q_;
+        if (qq.timed) qq.clock.now_ms = at;
+      }
+      typename Raft::Hosting h;
+      HostedStep sinks;
+      if (!closes_.empty()) h.has_close = true, h.close = closes_.front().groups, sinks.close = closes_.front().sink, sinks.close_asked = closes_.front().asked;
+      if (!opens_.empty()) {
+        const HostingAsk& o = opens_.front();
+        h.has_open = true, h.open = o.groups, h.has_self = !o.self_slots.empty(), h.self_slots = o.self_slots;
+        sinks.open = o.sink, sinks.open_asked = o.asked;
+      }
+      sinks.has_close = h.has_close, sinks.has_open = h.has_open;
+      r->step_node_hosted(at, flags, poll_q_ ? &qq : nullptr, awaited ? &a : nullptr, looked, list.data(), list.size(), progress, h);
+      // (a refused step keeps its requests queued)
+      if (looked) lookups_.erase(lookups_.begin(), lookups_.begin() + (std::ptrdiff_t)take), looked_slices_.push_back(std::move(slices));
+      if (h.has_close) closes_.pop_front();
+      if (h.has_open) opens_.pop_front();
+      hosted_sinks_.push_back(std::move(sinks));
+    };
+    view_hosted_ = [this, r]() {
+      const typename Raft::HostingVerdict v = r->node_hosting();
+      const HostedStep s = std::move(hosted_sinks_.front());
+      hosted_sinks_.pop_front();
+      if (!v.attached) return;
+      const bool close_first = !s.has_open || (s.has_close && s.close_asked < s.open_asked);
+      for (int k = 0; k < 2; k++) {
+        const bool close = (k == 0) == close_first;
+        if (close && s.has_close && s.close) s.close(!v.close_refused, v.redone);
+        if (!close && s.has_open && s.open) s.open(!v.open_refused, v.redone);
+      }
+    };
+    sync_hosted_ = [this, r](uint64_t at) {  // (nothing is outstanding: the synchronous calls, in the order they were asked)
+      while (!closes_.empty() || !opens_.empty()) {
+        const bool close = opens_.empty() || (!closes_.empty() && closes_.front().asked < opens_.front().asked);
+        std::deque<HostingAsk>& queue = close ? closes_ : opens_;
+        const HostingAsk q = std::move(queue.front());
+        queue.pop_front();
+        // (a listed slot in the wrong state - what a step reports as refused - is found by asking; whatever else refuses the
+        // call, commands that are still queued for instance, is the caller's to hear of: it throws)
+        bool applied = true;
+        if (!q.groups.empty()) {
+          const typename Raft::GroupStates now = r->lookup(q.groups.data(), q.groups.size(), false);
+          for (const jg_group_state& s : now.rows) applied = applied && (s.fault == JG_FAULT_VACANT) == !close;
+        }
+        if (applied) {
+          if (close) r->close_groups(q.groups);
+          else r->open_groups(q.groups, at, q.self_slots.empty() ? nullptr : &q.self_slots);
+        }
+        if (q.sink) q.sink(applied, false);
+      }
+    };
+  }
   std::deque<Message> local_;
   std::map<uint64_t, Response> requests_;
   std::map<std::pair<uint32_t, BlockId>, uint64_t> notifications_;
